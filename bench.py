@@ -5,11 +5,19 @@ One "step" = one MCMC iteration over the whole per-GPU BlockEnsemble:
   draw_proposal_path!(be)            (pCN + guided Euler–Maruyama + Girsanov weight, device RNG)
   accept_reject_proposal_path!(be,i) (per-block MH test, selector swaps, histories)
   fetch_ll(be) + accepted count      (deterministic reduction; RCCL all-gather over ranks)
-i.e. the caller loop of /root/reference/docs/src/tutorials/biblock/smoothing.md:40-44 at
+i.e. the caller loop of the reference's docs/src/tutorials/biblock/smoothing.md:40-44 at
 BlockEnsemble level (src/block_ensemble.jl:50,63-67,140).  Throughput unit: bridge-segment
 Euler steps (one grid increment of one segment) per second, whole job.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5]
+                  [--dump-outputs DIR] [--full]
+A plain run sets up, runs the W warm-up steps, times the K steps and prints the result line
+(value, ms_per_step, accept rate, configuration).  --dump-outputs DIR then writes what the timed
+call left after its last step as DIR/<name>.npy (dump_outputs below); the inputs and the random
+streams are seeded, so two builds run with the same arguments can be compared array for array.
+--full adds every measurement that takes runs of its own: the draw kernel's event timing and
+the roofline figures, repeats of the timed call, the caller's separate-call loop, the per-rank
+diagnostics of an N-GPU run and the CPU baseline with its decision-for-decision comparison.
 Multi-GPU: one process per GPU, weak scaling: rank r owns recording shard r of a global
 ensemble of N x B blocks (RNG keyed by global segment ids, diffusionmcmctools.jl_amd/shard.py);
 the only collective is fetch_ll's RCCL all-gather of 3 doubles per iteration.  Under
@@ -268,6 +276,35 @@ def rank_diagnostics(dist, world, k_ms, allgather_us, rccl_nranks):
             "per_rank": vals}
 
 
+DUMP_PATH_BYTES = 48 << 20  # bound of paths.npy + paths_rows.npy (every dump stays below 64 MB)
+
+
+def dump_outputs(dirname, ens, lay, B, res):
+    """--dump-outputs: what a caller holds after the timed call, read back right after it (before
+    any --full measurement moves the state on), as float64 .npy files under `dirname`:
+      mcmc_run.npy    (K, 3)  the timed call's return value: fetch_ll, fetch_ll°, accepted count
+                              of each of the K steps (the last row is the last step's)
+      ll.npy, ll_prop.npy (B,) every block's ll and ll° after the last step
+      paths.npy       (P, d)  the accepted paths X after the last step, all P path points of this
+                              rank's blocks — or, above DUMP_PATH_BYTES, the rows listed in
+                              paths_rows.npy: a fixed sample (seed 0) of the P rows, ascending
+    Rank 0 writes its own shard."""
+    from diffusionmcmctools_amd import _lib as L
+    os.makedirs(dirname, exist_ok=True)
+    out = {"mcmc_run": np.array(res, dtype=np.float64),
+           "ll": ens.get_block_state(lay, L.BLK_LL, 0, B),
+           "ll_prop": ens.get_block_state(lay, L.BLK_LLPROP, 0, B)}
+    X = ens.download_paths(L.U, 0)
+    rows = DUMP_PATH_BYTES // (8 * (X.shape[1] + 1))
+    if X.shape[0] > rows:
+        idx = np.sort(np.random.default_rng(0).choice(X.shape[0], rows, replace=False))
+        out["paths_rows"] = idx.astype(np.float64)
+        X = X[idx]
+    out["paths"] = X
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
@@ -298,6 +335,13 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="c2", choices=sorted(WORKLOADS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed call left after its last "
+                         "step as DIR/<name>.npy (float64, below 64 MB; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, every measurement that takes runs of its own: "
+                         "kernel event timing and rooflines, repeats, the separate-call loop, "
+                         "per-rank diagnostics, the CPU baseline (the options below shape them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--mapping", default="auto", choices=["auto", "lane", "wave"],
@@ -343,8 +387,11 @@ def main(argv=None):
     from diffusionmcmctools_amd import workloads as W
 
     w = build_workload(args.config, rank)
-    w.meta["hist_len"] = (args.warmup + args.steps * (3 + max(args.repeats, 0)) + EXTRA_ITERS +
-                          CPU_MAX_ITERS + 2 * args.calls_iters)
+    # history slots: one per iteration this run can reach (a plain run: warm-up + timed steps)
+    w.meta["hist_len"] = args.warmup + args.steps
+    if args.full:
+        w.meta["hist_len"] += (args.steps * (2 + max(args.repeats, 0)) + EXTRA_ITERS +
+                               CPU_MAX_ITERS + 2 * args.calls_iters)
     mapping = {"auto": L.MAP_AUTO, "lane": L.MAP_LANE, "wave": L.MAP_WAVE}[args.mapping]
     ens = dmt.Ensemble(w.model.kind, w.d, w.m, w.n_points, precision=w.precision,
                        seed=ens_seed, device=local_rank, grid_shared=w.grid_shared,
@@ -395,81 +442,75 @@ def main(argv=None):
     recent = L.recent_kernels()  # the kernels the timed call dispatched (dmt_recent_kernels)
     n_acc = float(res[:, 2].sum())  # read before any later run of this length reuses the buffer
     done = args.warmup + args.steps  # iterations run so far
-    # The dominant kernel's launch duration: HIP events recorded on libdmt's stream around the
-    # launches of the same K steps, run twice right after the timed region (same launch shape,
-    # same state; the first event-recording call is not the one averaged alone).
-    ens.set_timing(True, kernels=[L.K_DRAW])
-    for _ in range(2):
-        if args.api == "calls":
-            separate_calls(ens, lay, B, done + 1, args.steps, world > 1, python=False)
-        else:
-            ens.mcmc_run(lay, 0, B, done + 1, args.steps)
-        done += args.steps
-    ens.sync()
-    k_ms, k_n = ens.get_timing(L.K_DRAW)  # k_n counts iterations (persistent) or launches
-    k_ms /= 2.0  # per K steps
-    persist = w.model.kind == L.MODEL_OU and os.environ.get("DMT_MCMC_PERSIST", "1") != "0"
-    a_ms = a_n = 0
-    if not persist:
-        # the accept+reduce kernel, timed on a few extra iterations
-        ens.set_timing(True, kernels=[L.K_ACCEPT])
-        ens.mcmc_run(lay, 0, B, done + 1, EXTRA_ITERS)
-        a_ms, a_n = ens.get_timing(L.K_ACCEPT)
-        done += EXTRA_ITERS
-    ens.set_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ens, lay, B, res)
     if dist is not None:
         import torch
         t = torch.tensor([el], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    persist = w.model.kind == L.MODEL_OU and os.environ.get("DMT_MCMC_PERSIST", "1") != "0"
 
-    # repeats of the same K steps (median and mean beside the headline)
+    # --full: the measurements beside the headline, each with runs of its own after the timed one
+    k_ms = a_ms = a_n = 0
     rep_ms = []
-    for _ in range(max(args.repeats, 0)):
-        barrier()
-        t1 = time.perf_counter()
-        ens.mcmc_run(lay, 0, B, done + 1, args.steps)
-        barrier()
-        rep_ms.append((time.perf_counter() - t1) / args.steps * 1e3)
-        done += args.steps
-    # the caller's separate-call loop beside the fused headline
-    calls = None
-    if args.calls_iters > 0 and args.api == "run":
-        c_us, py_us, _ = separate_calls(ens, lay, B, done + 1, args.calls_iters, world > 1)
-        done += 2 * args.calls_iters
-        calls = {"loop": "draw_proposal_path!(be); accept_reject_proposal_path!(be, i); "
-                         "fetch_ll(be); fetch_ll°(be) as separate C-ABI calls",
-                 "us_per_iteration_c": c_us, "us_per_iteration_python_ctypes": py_us,
-                 "steps_per_s_c": w.steps_per_iter / (c_us * 1e-6),
-                 "iterations": args.calls_iters,
-                 "fused_launch_per_iteration": os.environ.get("DMT_DEFER", "1") != "0"}
-    diag = None
-    if dist is not None:
-        # all-gather cost per call: global (collective) minus local fetch_ll, 20 calls each
+    calls = diag = None
+    if args.full:
+        # The dominant kernel's launch duration: HIP events recorded on libdmt's stream around
+        # the launches of the same K steps, run twice right after the timed region (same launch
+        # shape, same state; the first event-recording call is not the one averaged alone).
+        ens.set_timing(True, kernels=[L.K_DRAW])
+        for _ in range(2):
+            if args.api == "calls":
+                separate_calls(ens, lay, B, done + 1, args.steps, world > 1, python=False)
+            else:
+                ens.mcmc_run(lay, 0, B, done + 1, args.steps)
+            done += args.steps
         ens.sync()
-        t1 = time.perf_counter()
-        for _ in range(20):
-            ens.fetch_ll(lay, 0, B, 0, local=True)
-        loc = time.perf_counter() - t1
-        dist.barrier()
-        t1 = time.perf_counter()
-        for _ in range(20):
-            ens.fetch_ll(lay, 0, B, 0)
-        glob = time.perf_counter() - t1
-        diag = rank_diagnostics(dist, world, k_ms, (glob - loc) / 20 * 1e6, rccl_nranks)
+        k_ms, k_n = ens.get_timing(L.K_DRAW)  # k_n counts iterations (persistent) or launches
+        k_ms /= 2.0  # per K steps
+        if not persist:
+            # the accept+reduce kernel, timed on a few extra iterations
+            ens.set_timing(True, kernels=[L.K_ACCEPT])
+            ens.mcmc_run(lay, 0, B, done + 1, EXTRA_ITERS)
+            a_ms, a_n = ens.get_timing(L.K_ACCEPT)
+            done += EXTRA_ITERS
+        ens.set_timing(False)
+
+        # repeats of the same K steps (median and mean beside the headline)
+        for _ in range(max(args.repeats, 0)):
+            barrier()
+            t1 = time.perf_counter()
+            ens.mcmc_run(lay, 0, B, done + 1, args.steps)
+            barrier()
+            rep_ms.append((time.perf_counter() - t1) / args.steps * 1e3)
+            done += args.steps
+        # the caller's separate-call loop beside the fused headline
+        if args.calls_iters > 0 and args.api == "run":
+            c_us, py_us, _ = separate_calls(ens, lay, B, done + 1, args.calls_iters, world > 1)
+            done += 2 * args.calls_iters
+            calls = {"loop": "draw_proposal_path!(be); accept_reject_proposal_path!(be, i); "
+                             "fetch_ll(be); fetch_ll°(be) as separate C-ABI calls",
+                     "us_per_iteration_c": c_us, "us_per_iteration_python_ctypes": py_us,
+                     "steps_per_s_c": w.steps_per_iter / (c_us * 1e-6),
+                     "iterations": args.calls_iters,
+                     "fused_launch_per_iteration": os.environ.get("DMT_DEFER", "1") != "0"}
+        if dist is not None:
+            # all-gather cost per call: global (collective) minus local fetch_ll, 20 calls each
+            ens.sync()
+            t1 = time.perf_counter()
+            for _ in range(20):
+                ens.fetch_ll(lay, 0, B, 0, local=True)
+            loc = time.perf_counter() - t1
+            dist.barrier()
+            t1 = time.perf_counter()
+            for _ in range(20):
+                ens.fetch_ll(lay, 0, B, 0)
+            glob = time.perf_counter() - t1
+            diag = rank_diagnostics(dist, world, k_ms, (glob - loc) / 20 * 1e6, rccl_nranks)
 
     steps_total = w.steps_per_iter * args.steps * world
     value = steps_total / el
-    # launches of the dominant kernel in the timed region: one per iteration, or (persistent,
-    # dmt_mcmc_run) one per chunk of iterations (dmt_runtime.hip: ≤ 64 MiB of partials)
-    it_per_launch = (min(args.steps, max(1, (64 << 20) // (24 * B)))
-                     if persist and args.api == "run" else 1)
-    launches = -(-args.steps // it_per_launch)
-    k_avg_s = (k_ms / launches) * 1e-3          # average launch duration
-    k_iter_s = (k_ms / max(args.steps, 1)) * 1e-3
-    bytes_iter = algorithmic_bytes_per_step(w) * w.steps_per_iter
-    bytes_launch = bytes_iter * it_per_launch
-    achieved = bytes_launch / k_avg_s / 1e9 if k_avg_s > 0 else 0.0
     accept_rate = n_acc / (B * world * args.steps)  # n_acc is already global (fetch_ll over ranks)
     # the mapping libdmt resolves for MAP_AUTO (kAutoWaveMaxRecordings, dmt_internal.h)
     wave = args.mapping == "wave" or (args.mapping == "auto" and len(w.n_points) <= 8192)
@@ -498,21 +539,8 @@ def main(argv=None):
     # the draw kernel the library actually dispatched in the timed call, when it reports one
     # (the restatement above is the fallback for a library without dmt_recent_kernels)
     kname = dispatched_kernel(recent) or kname
-    # committed profile summaries of THIS source tree only (scripts/provenance.py)
-    tr, traffic_stale = committed_summary("traffic", args.config, kname)
-    traffic = tr["traffic_bytes_per_unit"] * it_per_launch if tr else None  # per launch
-    traffic_src = tr["source"] if tr else None
-    issue, issue_stale = committed_summary("issue", args.config, kname)
-    rp, rp_stale = committed_summary("kstats", args.config, kname)
-    rp_us = None
-    if rp is not None and rp.get("units_per_launch", 1) == it_per_launch:  # same launch shape
-        rp_us = rp["avg_us"]
     if rank == 0:
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu = cpu_baseline(w, ens, lay, done + 1, budget_s=args.cpu_budget)
         desc, dtype = WORKLOADS[args.config]
-        frac = achieved / PEAK_HBM_GBS
         line = {
             "metric": "bridge-segment Euler steps/sec/GPU; accept-rate vs CPU ref",
             "value": value,
@@ -540,6 +568,33 @@ def main(argv=None):
                        "rng": "device Philox4x32-10 + Box-Muller (perf mode)"},
             "per_gpu": value / world,
             "accept_rate": accept_rate,
+            "api": args.api,
+        }
+    if args.full and rank == 0:
+        # launches of the dominant kernel in the timed region: one per iteration, or (persistent,
+        # dmt_mcmc_run) one per chunk of iterations (dmt_runtime.hip: ≤ 64 MiB of partials)
+        it_per_launch = (min(args.steps, max(1, (64 << 20) // (24 * B)))
+                         if persist and args.api == "run" else 1)
+        launches = -(-args.steps // it_per_launch)
+        k_avg_s = (k_ms / launches) * 1e-3          # average launch duration
+        k_iter_s = (k_ms / max(args.steps, 1)) * 1e-3
+        bytes_iter = algorithmic_bytes_per_step(w) * w.steps_per_iter
+        bytes_launch = bytes_iter * it_per_launch
+        achieved = bytes_launch / k_avg_s / 1e9 if k_avg_s > 0 else 0.0
+        # committed profile summaries of THIS source tree only (scripts/provenance.py)
+        tr, traffic_stale = committed_summary("traffic", args.config, kname)
+        traffic = tr["traffic_bytes_per_unit"] * it_per_launch if tr else None  # per launch
+        traffic_src = tr["source"] if tr else None
+        issue, issue_stale = committed_summary("issue", args.config, kname)
+        rp, rp_stale = committed_summary("kstats", args.config, kname)
+        rp_us = None
+        if rp is not None and rp.get("units_per_launch", 1) == it_per_launch:  # same launch shape
+            rp_us = rp["avg_us"]
+        cpu = None
+        if world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_baseline(w, ens, lay, done + 1, budget_s=args.cpu_budget)
+        frac = achieved / PEAK_HBM_GBS
+        line.update({
             # bound: what the counters show for this kernel (issue summary), HBM otherwise
             "roofline": {"bound": (issue or {}).get("bound", "hbm"), "achieved": achieved,
                          "peak": PEAK_HBM_GBS,
@@ -572,7 +627,6 @@ def main(argv=None):
                          "limiter": (issue or {}).get("limiter"),
                          "issue": issue},
             "accept_kernel_avg_us": (a_ms / a_n) * 1e3 if a_n else None,
-            "api": args.api,
             "repeats": {"n": len(rep_ms),
                         "ms_per_step_median": float(np.median(rep_ms)) if rep_ms else None,
                         "ms_per_step_mean": float(np.mean(rep_ms)) if rep_ms else None,
@@ -581,11 +635,12 @@ def main(argv=None):
             "separate_calls": calls,
             "rank_diagnostics": diag,
             "cpu_baseline": cpu,
-        }
+        })
         if cpu is not None:
             line["accept_rate_cpu"] = cpu["accept_rate"]
             line["decisions_identical"] = cpu["decisions_identical"]
             line["decisions_total"] = cpu["decisions_total"]
+    if rank == 0:
         print(json.dumps(line), flush=True)
     ens.close()
     if dist is not None:

@@ -28,15 +28,15 @@ L2="VALU issue and dependency latency: the consumer's chain per iteration (scan,
 L5="two balanced latency-bound waves per tile, one per SIMD (1 024 waves): producer (normals, u.W packets, W° whole lines) and consumer (H, F rows, recursion, X° whole lines); drawing every normal twice adds 560 µs per draw, the consumer's arithmetic twice 215 µs (profiles/r06h); loads, stores and hand-off alone 865 µs (r06g)"
 L3="HBM throughput for its 6:3 read/write fp64 row mix with one wave per SIMD: a memory-only kernel of the same pattern runs 769-898 µs whatever the prefetch depth (profiles/r06f, scripts/c3_mem_probe.hip)"
 K5='k_block_ps_pk<dmt::Lorenz<float>, float, 4'; K3='k_block<dmt::FHN<double>, double, 0'
-python scripts/kstats_summary.py --trace $P/c2_kernel_trace.csv --kernel k_mcmc_resident_pc --config c2 --skip 5 --units-per-launch 20 --tree $P/tree.txt --command "rocprofv3 --kernel-trace --stats -- python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --repeats 0 --calls-iters 0 (dispatches: 5 one-iteration warm-up calls skipped; the timed call and the two event re-runs)" --out profiles/${A}_kstats_c2.json > /dev/null
+python scripts/kstats_summary.py --trace $P/c2_kernel_trace.csv --kernel k_mcmc_resident_pc --config c2 --skip 5 --units-per-launch 20 --tree $P/tree.txt --command "rocprofv3 --kernel-trace --stats -- python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --repeats 0 --calls-iters 0 (dispatches: 5 one-iteration warm-up calls skipped; the timed call and the two event re-runs)" --out profiles/${A}_kstats_c2.json > /dev/null
 python scripts/pmc_traffic.py --fetch $P/pmc_c2_fetch.csv --write $P/pmc_c2_write.csv --kernel k_mcmc_resident_pc --calib-fetch $P/pmc_calib_fetch.csv --calib-write $P/pmc_calib_write.csv --config c2 --units-per-launch 20 --skip 20 --tree $P/tree.txt --out profiles/${A}_traffic_c2.json > /dev/null
-python scripts/issue_summary.py --kernel k_mcmc_resident_pc --config c2 --iters 20 --blocks 1024 --steps-per-block 500 --simds 1024 --skip 20 --csv $P/c2_sq1.csv $P/c2_sq2.csv --tree $P/tree.txt --command "rocprofv3 --pmc <SQ pass> -- python bench.py --steps 20 --warmup 20 --no-cpu-baseline --repeats 0 --calls-iters 0 (20 one-iteration warm-up dispatches skipped)" --bound valu-latency --limiter "$L2" --out profiles/${A}_issue_c2.json > /dev/null
-python scripts/kstats_summary.py --trace $Q/c5_kernel_trace.csv --kernel "$K5" --config c5 --skip 3 --tree $Q/tree.txt --command "rocprofv3 --kernel-trace --stats -- python bench.py --config c5 --steps 20 --warmup 3 --no-cpu-baseline --calls-iters 0 --repeats 0 (the 3 warm-up draws skipped)" --out profiles/${B}_kstats_c5.json > /dev/null
-python scripts/kstats_summary.py --trace $Q/c3_kernel_trace.csv --kernel "$K3" --config c3 --skip 3 --tree $Q/tree.txt --command "rocprofv3 --kernel-trace --stats -- python bench.py --config c3 --steps 20 --warmup 3 --no-cpu-baseline --calls-iters 0 --repeats 0 (the 3 warm-up draws skipped)" --out profiles/${B}_kstats_c3.json > /dev/null
+python scripts/issue_summary.py --kernel k_mcmc_resident_pc --config c2 --iters 20 --blocks 1024 --steps-per-block 500 --simds 1024 --skip 20 --csv $P/c2_sq1.csv $P/c2_sq2.csv --tree $P/tree.txt --command "rocprofv3 --pmc <SQ pass> -- python bench.py --full --steps 20 --warmup 20 --no-cpu-baseline --repeats 0 --calls-iters 0 (20 one-iteration warm-up dispatches skipped)" --bound valu-latency --limiter "$L2" --out profiles/${A}_issue_c2.json > /dev/null
+python scripts/kstats_summary.py --trace $Q/c5_kernel_trace.csv --kernel "$K5" --config c5 --skip 3 --tree $Q/tree.txt --command "rocprofv3 --kernel-trace --stats -- python bench.py --full --config c5 --steps 20 --warmup 3 --no-cpu-baseline --calls-iters 0 --repeats 0 (the 3 warm-up draws skipped)" --out profiles/${B}_kstats_c5.json > /dev/null
+python scripts/kstats_summary.py --trace $Q/c3_kernel_trace.csv --kernel "$K3" --config c3 --skip 3 --tree $Q/tree.txt --command "rocprofv3 --kernel-trace --stats -- python bench.py --full --config c3 --steps 20 --warmup 3 --no-cpu-baseline --calls-iters 0 --repeats 0 (the 3 warm-up draws skipped)" --out profiles/${B}_kstats_c3.json > /dev/null
 python scripts/pmc_traffic.py --fetch $Q/pmc_c5_fetch.csv --write $Q/pmc_c5_write.csv --kernel "$K5" --calib-fetch $P/pmc_calib_fetch.csv --calib-write $P/pmc_calib_write.csv --calib-kernel 'k_stream<float>' --config c5 --skip 2 --tree $Q/tree.txt --out profiles/${B}_traffic_c5.json > /dev/null
 python scripts/pmc_traffic.py --fetch $Q/pmc_c3_fetch.csv --write $Q/pmc_c3_write.csv --kernel "$K3" --calib-fetch $P/pmc_calib_fetch.csv --calib-write $P/pmc_calib_write.csv --calib-kernel 'k_stream<double>' --config c3 --skip 2 --tree $Q/tree.txt --out profiles/${B}_traffic_c3.json > /dev/null
-python scripts/issue_summary.py --kernel "$K5" --config c5 --iters 1 --blocks 32768 --steps-per-block 2000 --simds 1024 --skip 2 --csv $Q/c5_sq1.csv $Q/c5_sq2.csv --tree $Q/tree.txt --command "rocprofv3 --pmc <SQ pass> -- python bench.py --config c5 --steps 4 --warmup 2 --no-cpu-baseline --calls-iters 0 --repeats 0 (the 2 warm-up draws skipped)" --bound hbm --limiter "$L5" --out profiles/${B}_issue_c5.json > /dev/null
-python scripts/issue_summary.py --kernel "$K3" --config c3 --iters 1 --blocks 65536 --steps-per-block 1000 --simds 1024 --skip 2 --csv $Q/c3_sq1.csv $Q/c3_sq2.csv --tree $Q/tree.txt --command "rocprofv3 --pmc <SQ pass> -- python bench.py --config c3 --steps 4 --warmup 2 --no-cpu-baseline --calls-iters 0 --repeats 0 (the 2 warm-up draws skipped)" --bound hbm --limiter "$L3" --out profiles/${B}_issue_c3.json > /dev/null
+python scripts/issue_summary.py --kernel "$K5" --config c5 --iters 1 --blocks 32768 --steps-per-block 2000 --simds 1024 --skip 2 --csv $Q/c5_sq1.csv $Q/c5_sq2.csv --tree $Q/tree.txt --command "rocprofv3 --pmc <SQ pass> -- python bench.py --full --config c5 --steps 4 --warmup 2 --no-cpu-baseline --calls-iters 0 --repeats 0 (the 2 warm-up draws skipped)" --bound hbm --limiter "$L5" --out profiles/${B}_issue_c5.json > /dev/null
+python scripts/issue_summary.py --kernel "$K3" --config c3 --iters 1 --blocks 65536 --steps-per-block 1000 --simds 1024 --skip 2 --csv $Q/c3_sq1.csv $Q/c3_sq2.csv --tree $Q/tree.txt --command "rocprofv3 --pmc <SQ pass> -- python bench.py --full --config c3 --steps 4 --warmup 2 --no-cpu-baseline --calls-iters 0 --repeats 0 (the 2 warm-up draws skipped)" --bound hbm --limiter "$L3" --out profiles/${B}_issue_c3.json > /dev/null
 python - "$A" "$B" <<'PY'
 import csv, json, sys
 A, B = sys.argv[1:3]
