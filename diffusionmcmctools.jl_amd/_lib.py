@@ -57,6 +57,8 @@ SYMBOLS = [
     "dmt_rng_state", "dmt_set_rng_state", "dmt_combine_rank_partials",
     "dmt_set_service", "dmt_service_stats", "dmt_set_proposal_law_cc", "dmt_upload_aux_a",
     "dmt_guiding_linear_tda",
+    "dmt_get_rho", "dmt_set_rho", "dmt_accept_counts", "dmt_adapt_rho", "dmt_set_run_adaptation",
+    "dmt_adapt_rule",
 ]
 
 
@@ -78,6 +80,13 @@ class dmt_structure(C.Structure):
 class dmt_config(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("device", C.c_int32), ("grid_shared", C.c_int32),
                 ("mapping", C.c_int32)]
+
+
+class dmt_adapt_config(C.Structure):
+    """The adaptation of the pCN memory ρ (include/dmt.h, "pCN memory ρ")."""
+    _fields_ = [("every", C.c_int64), ("lo", C.c_double), ("hi", C.c_double),
+                ("delta0", C.c_double), ("delta_max", C.c_double), ("rho_min", C.c_double),
+                ("rho_max", C.c_double), ("until", C.c_int64)]
 
 
 if not os.path.exists(LIB_PATH):
@@ -157,6 +166,12 @@ _SIGS = {
     "dmt_set_proposal_law_cc": [_P, _i32, _i64, _i64, _i32, _P, _P, _i32, _i32, _P, _P],
     "dmt_service_stats": [_P, C.POINTER(_u64)],
     "dmt_recent_kernels": [C.c_char_p, _i64],
+    "dmt_get_rho": [_P, _i32, _i64, _i64, _pd],
+    "dmt_set_rho": [_P, _i32, _i64, _i64, _pd],
+    "dmt_accept_counts": [_P, _i32, _i64, _i64, _i64, _i64, _pi64],
+    "dmt_adapt_rho": [_P, _i32, _i64, _i64, _i64, C.POINTER(dmt_adapt_config), _pi64],
+    "dmt_set_run_adaptation": [_P, _i32, C.POINTER(dmt_adapt_config)],
+    "dmt_adapt_rule": [C.POINTER(dmt_adapt_config), _i64, _i64, _pd, _pi64, _pd, _pd],
 }
 for _name, _args in _SIGS.items():
     _f = getattr(lib, _name)

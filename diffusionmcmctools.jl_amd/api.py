@@ -616,8 +616,45 @@ class _BlockRange:
     def accpt_rate(self, rng):
         """Per block: mean of accpt_history over the 1-based iterations in ``rng``
         (src/biblock.jl:230)."""
+        counts = getattr(self._ens, "accept_counts", None)
+        if isinstance(rng, range) and rng.step == 1 and len(rng) > 0 and counts is not None:
+            # a contiguous window: summed on the device, the history stays there
+            return self._call("accept_counts", rng.start, rng.stop - 1) / len(rng)
         idx = np.asarray(list(rng), dtype=np.int64) - 1
         return self.accpt_history[idx].sum(axis=0) / len(idx)
+
+    # ---- pCN memory ρ (the mutable field bb.ρ, src/biblock.jl:43-47) and its adaptation
+    def _get_rho(self):
+        get = getattr(self._ens, "get_rho", None)
+        if get is None:  # an engine of the test seam without ρ access: the constructor's value
+            return np.atleast_1d(np.array(self._rho0, dtype=np.float64))
+        return get(self._layout, self._b0, self._b1)
+
+    def _set_rho(self, v):
+        self._ens.set_rho(self._layout, self._b0, self._b1, v)
+
+    def adapt_rho(self, mcmciter, every=None, accept_band=(0.15, 0.35), delta0=0.5,
+                  delta_max=0.5, rho_bounds=(0.01, 0.9999), until=0):
+        """One adaptation of every block's ρ after iteration ``mcmciter`` from its own
+        acceptance count over the last ``every`` iterations (default: ``mcmciter`` itself, i.e.
+        all iterations so far) — the rule of include/dmt.h ("pCN memory ρ"), on the device.
+        Returns the number of blocks whose ρ changed."""
+        from .engine import adapt_config
+        cfg = adapt_config(mcmciter if every is None else every, accept_band[0], accept_band[1],
+                           delta0, delta_max, rho_bounds[0], rho_bounds[1], until)
+        return self._call("adapt_rho", mcmciter, cfg)
+
+    def set_run_adaptation(self, every, accept_band=(0.15, 0.35), delta0=0.5, delta_max=0.5,
+                           rho_bounds=(0.01, 0.9999), until=0):
+        """Adapt ρ inside every later :meth:`mcmc_run` of this object's layout: after each
+        iteration i with i % every == 0 (and i <= ``until`` when given) every block of the run's
+        range moves logit ρ by ±min(delta_max, delta0/√(i/every)) when its acceptance rate over
+        the last ``every`` iterations left ``accept_band``, clamped to ``rho_bounds`` — without
+        a host round trip.  ``every = 0``: off.  Needs ``ll_hist_len`` > 0."""
+        from .engine import adapt_config
+        cfg = None if not every else adapt_config(every, accept_band[0], accept_band[1], delta0,
+                                                  delta_max, rho_bounds[0], rho_bounds[1], until)
+        self._ens.set_run_adaptation(self._layout, cfg)
 
     # ---- parameter updates (biblock.jl:334-375, block_collection.jl:306-334)
     def set_proposal_law(self, theta=None, H=None, F=None, laws=None, Hb=None, Fb=None,
@@ -779,11 +816,21 @@ class BiBlock(_BlockRange):
 
     def _init_view(self, ens, layout, b, hist_len, is_last, rho, segments, rec=0, model=None):
         super().__init__(ens, layout, b, b + 1, hist_len)
-        self.is_last, self.rho, self.segments = bool(is_last), float(rho), segments
+        self.is_last, self._rho0, self.segments = bool(is_last), float(rho), segments
         self.rec, self.model = int(rec), model
         # bb.b / bb.b° (src/biblock.jl:43-46): the accepted and the proposal Block views
         self.b = Block(self, L.U)
         self.b_prop = Block(self, L.UPROP)
+
+    @property
+    def rho(self):
+        """``bb.ρ`` (src/biblock.jl:43-47): read from the device; assigning it sets the device's
+        value, which the next draw uses (histories, ll and ll° stay)."""
+        return float(self._get_rho()[0])
+
+    @rho.setter
+    def rho(self, v):
+        self._set_rho(float(v))
 
     def fetch_ll(self):
         return float(self.ll[0])
@@ -825,6 +872,17 @@ class BlockCollection(_BlockRange):
     def _init_view(self, ens, layout, b0, blocks, hist_len):
         super().__init__(ens, layout, b0, b0 + len(blocks), hist_len)
         self.blocks = blocks
+        self._rho0 = [b._rho0 for b in blocks]
+
+    @property
+    def rho(self):
+        """ρ of every block (an array, read from the device); assignable (a scalar or one
+        value per block)."""
+        return self._get_rho()
+
+    @rho.setter
+    def rho(self, v):
+        self._set_rho(v)
 
 
 class BlockEnsemble(_BlockRange):
@@ -867,6 +925,7 @@ class BlockEnsemble(_BlockRange):
         nb = len(sf)
         super().__init__(ens, layout, 0, nb, ll_hist_len)
         self._global = True
+        self._rho0 = rhos
         self.se = se
         self.recordings = []
         b = 0
@@ -881,6 +940,16 @@ class BlockEnsemble(_BlockRange):
 
     def num_recordings(self):
         return len(self.recordings)
+
+    @property
+    def rho(self):
+        """ρ of every block of the ensemble, recording-major (an array, read from the device);
+        assignable (a scalar or one value per block)."""
+        return self._get_rho()
+
+    @rho.setter
+    def rho(self, v):
+        self._set_rho(v)
 
     def ll_of_accepted(self, i):
         flat = super().ll_of_accepted(i)

@@ -166,6 +166,51 @@ struct AcceptArgs {
   uint8_t* acc_out;  // [b1-b0] or nullptr
 };
 
+// One adaptation of the pCN memory ρ (include/dmt.h, "pCN memory ρ"): what the host derives
+// from the config and the iteration — κ_up = exp(δ), κ_dn = exp(−δ) by the host's libm, the band
+// in whole accepted iterations and the clamp — and the kernel takes as plain numbers.
+struct AdaptStep {
+  double k_up, k_dn;
+  int64_t n_lo, n_hi;
+  double rho_min, rho_max;
+};
+
+// The rule, the one definition the kernel (k_adapt_rho), the host entry point (dmt_adapt_rule)
+// and the tests share: count c of a block → its new ρ and sqrt(1 − ρ²).  Returns false, leaving
+// both untouched, when c lies in the band.  Every operation is a separately rounded fp64 *, +, /
+// or sqrt (the build has -ffp-contract=off), so host and device give the same bits; the clamp is
+// written as comparisons, so a NaN quotient (κ overflowed or underflowed at ρ = 1) lands on
+// rho_min on both sides.
+__host__ __device__ __forceinline__ bool adapt_rule(const AdaptStep& s, int64_t c, double* rho,
+                                                    double* srho) {
+  double kap;
+  if (c < s.n_lo) kap = s.k_up;
+  else if (c > s.n_hi) kap = s.k_dn;
+  else return false;
+  const double r = *rho;
+  const double num = kap * r;
+  const double den = num + (1.0 - r);
+  double rn = num / den;
+  rn = rn > s.rho_min ? rn : s.rho_min;
+  rn = rn < s.rho_max ? rn : s.rho_max;
+  *rho = rn;
+  *srho = sqrt(1.0 - rn * rn);
+  return true;
+}
+
+// k_accept_counts / k_adapt_rho: blocks [b0, b1), history rows i0..i1 (1-based, inclusive)
+struct AdaptArgs {
+  int64_t b0, b1, nblocks;
+  const uint8_t* acc_hist;  // [hist_len][nblocks]
+  int64_t i0, i1;
+  int64_t* counts;          // k_accept_counts: [b1 - b0]
+  AdaptStep step;           // k_adapt_rho
+  double* rho;              // [nblocks]
+  double* srho;
+  BlkInfo* binfo;           // [nblocks]: its rho / srho fields
+  uint32_t* n_changed;      // the blocks whose ρ changed are added here
+};
+
 // The resident MCMC service (include/dmt.h "deferred draws"): a launch of the
 // register-resident producer/consumer kernel that runs the iterations the host posts one at a
 // time, keeping every block's state in registers between the caller's separate calls.
@@ -280,6 +325,11 @@ hipError_t launch_invsolve_kernel(const ModelKey& k, int mapping, const void* ar
 hipError_t launch_pathll_kernel(const ModelKey& k, int mapping, const void* args, int64_t nwaves,
                                 hipStream_t s);
 hipError_t launch_accept(const AcceptArgs& a, hipStream_t s);
+hipError_t launch_accept_counts(const AdaptArgs& a, hipStream_t s);
+hipError_t launch_adapt_rho(const AdaptArgs& a, hipStream_t s);
+// dmt_set_rho: binfo[b].rho / .srho ← rho[b] / srho[b] for blocks [b0, b1)
+hipError_t launch_sync_binfo_rho(BlkInfo* binfo, const double* rho, const double* srho, int64_t b0,
+                                 int64_t b1, hipStream_t s);
 // dmt_mcmc_run for linear drifts: n_iter iterations in one launch (k_mcmc_scan), per-iteration
 // (ll, ll°, accepted) partials to part[n_iter][3][nwaves]; then their fetch_ll trees
 // (resident: every block is one segment of ≤ kResidentMaxSteps steps and d ≤ 2 —

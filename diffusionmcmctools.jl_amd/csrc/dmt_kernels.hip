@@ -4358,6 +4358,66 @@ __global__ __launch_bounds__(256) void k_accept(const AcceptArgs a) {
   }
   if (a.acc_out) a.acc_out[blk - a.b0] = acc ? 1 : 0;
 }
+
+// ---------------------------------------------------------------- pCN memory ρ (include/dmt.h)
+// Accepted iterations of block blk among history rows i0..i1 (1-based, inclusive): one lane per
+// block, so consecutive lanes read consecutive bytes of a row; four rows per trip keep four
+// loads in flight.  A row holds 0 / 1, or whatever dmt_set_block_state wrote: non-zero counts as
+// accepted, as the Bool history it mirrors.
+__device__ __forceinline__ int64_t accept_window_count(const uint8_t* __restrict__ hist,
+                                                       int64_t nblocks, int64_t blk, int64_t i0,
+                                                       int64_t i1) {
+  const uint8_t* p = hist + (i0 - 1) * nblocks + blk;
+  int64_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+  int64_t i = i0;
+  for (; i + 3 <= i1; i += 4, p += 4 * nblocks) {
+    const uint8_t v0 = p[0], v1 = p[nblocks], v2 = p[2 * nblocks], v3 = p[3 * nblocks];
+    c0 += v0 != 0;
+    c1 += v1 != 0;
+    c2 += v2 != 0;
+    c3 += v3 != 0;
+  }
+  for (; i <= i1; ++i, p += nblocks) c0 += *p != 0;
+  return (c0 + c1) + (c2 + c3);
+}
+
+__global__ __launch_bounds__(256) void k_accept_counts(const AdaptArgs a) {
+  const int64_t blk = a.b0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (blk >= a.b1) return;
+  a.counts[blk - a.b0] = accept_window_count(a.acc_hist, a.nblocks, blk, a.i0, a.i1);
+}
+
+// One adaptation of ρ: the window count, then the shared rule (adapt_rule, dmt_internal.h); a
+// block in the band keeps ρ and sqrt(1 − ρ²) bit for bit.  Both copies of the pair are written:
+// the arrays (BlockArgs::rho / srho) and the block records (BlkInfo) — every draw kernel reads
+// one of the two at launch.
+__global__ __launch_bounds__(256) void k_adapt_rho(const AdaptArgs a) {
+  const int64_t blk = a.b0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (blk >= a.b1) return;
+  const int64_t c = accept_window_count(a.acc_hist, a.nblocks, blk, a.i0, a.i1);
+  const double rho0 = a.rho[blk];
+  double rho = rho0, srho = 0.0;
+  bool changed = false;
+  if (adapt_rule(a.step, c, &rho, &srho)) {
+    a.rho[blk] = rho;
+    a.srho[blk] = srho;
+    a.binfo[blk].rho = rho;
+    a.binfo[blk].srho = srho;
+    changed = rho != rho0;
+  }
+  // one atomic per wave: the first changed lane adds the wave's count
+  const unsigned long long m = __ballot(changed);
+  if (changed && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1)
+    atomicAdd(a.n_changed, (uint32_t)__popcll(m));
+}
+
+__global__ __launch_bounds__(256) void k_sync_binfo_rho(BlkInfo* binfo, const double* rho,
+                                                        const double* srho, int64_t b0, int64_t b1) {
+  const int64_t blk = b0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (blk >= b1) return;
+  binfo[blk].rho = rho[blk];
+  binfo[blk].srho = srho[blk];
+}
 #endif  // DMT_TU_COMMON
 
 // accept_reject + the first level of the fetch_ll tree in one pass: each thread decides its
@@ -6064,6 +6124,28 @@ hipError_t launch_accept(const AcceptArgs& a, hipStream_t s) {
   const int64_t n = a.b1 - a.b0;
   if (n <= 0) return hipSuccess;
   dlaunch(k_accept, dim3(nblk(n, 256)), dim3(256), s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_accept_counts(const AdaptArgs& a, hipStream_t s) {
+  const int64_t n = a.b1 - a.b0;
+  if (n <= 0) return hipSuccess;
+  dlaunch(k_accept_counts, dim3(nblk(n, 256)), dim3(256), s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_adapt_rho(const AdaptArgs& a, hipStream_t s) {
+  const int64_t n = a.b1 - a.b0;
+  if (n <= 0) return hipSuccess;
+  dlaunch(k_adapt_rho, dim3(nblk(n, 256)), dim3(256), s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_sync_binfo_rho(BlkInfo* binfo, const double* rho, const double* srho, int64_t b0,
+                                 int64_t b1, hipStream_t s) {
+  const int64_t n = b1 - b0;
+  if (n <= 0) return hipSuccess;
+  k_sync_binfo_rho<<<nblk(n, 256), 256, 0, s>>>(binfo, rho, srho, b0, b1);
   return hipGetLastError();
 }
 

@@ -78,10 +78,12 @@ struct Layout {
   uint8_t* d_acc = nullptr;
   uint8_t* d_crit = nullptr;    // [nblocks] set_proposal_law!'s critical-change flags
   uint32_t* d_ncrit = nullptr;  // their count
+  uint32_t* d_nadapt = nullptr;  // dmt_adapt_rho: blocks whose ρ changed
+  dmt_adapt_config adapt{};      // dmt_set_run_adaptation (every = 0: off)
   void release() {
     void* ps[] = {d_blk_off, d_binfo, d_blk_rec, d_gfirst, d_glast, d_term,  d_rho,
                   d_srho,    d_ll,    d_llp,     d_llh,    d_llph,  d_acch,  d_success,
-                  d_acc,     d_crit,  d_ncrit};
+                  d_acc,     d_crit,  d_ncrit,   d_nadapt};
     for (void* p : ps)
       if (p) (void)hipFree(p);
   }
@@ -815,6 +817,7 @@ dmt_status build_layout(dmt_ens* h, const int32_t* n_blocks, const int32_t* seg_
   DMT_TRY(ens_alloc(h, &L->d_success, nb));
   DMT_TRY(ens_alloc(h, &L->d_crit, nb));
   DMT_TRY(ens_alloc(h, &L->d_ncrit, 1));
+  DMT_TRY(ens_alloc(h, &L->d_nadapt, 1));
   DMT_TRY(ens_alloc(h, &L->d_acc, nb));
   if (L->hist_len > 0) {
     DMT_TRY(ens_alloc(h, &L->d_llh, L->hist_len * nb));
@@ -1628,6 +1631,173 @@ static int64_t grown_cap(int64_t need, int64_t cap, int64_t floor_) {
   return std::max({need, 2 * cap, floor_});
 }
 
+// ---------------------------------------------------------------- pCN memory ρ (include/dmt.h)
+static dmt_status check_adapt_config(const dmt_adapt_config* c) {
+  if (!c) return fail(DMT_ERR_INVALID, "null adaptation config");
+  if (c->every < 1) return fail(DMT_ERR_INVALID, "adaptation: every must be >= 1");
+  if (!(c->lo >= 0.0 && c->lo <= c->hi && c->hi <= 1.0))
+    return fail(DMT_ERR_INVALID, "adaptation: need 0 <= lo <= hi <= 1");
+  if (!(std::isfinite(c->delta0) && c->delta0 > 0.0 && std::isfinite(c->delta_max) && c->delta_max > 0.0))
+    return fail(DMT_ERR_INVALID, "adaptation: delta0 and delta_max must be finite and > 0");
+  if (!(c->rho_min >= 0.0 && c->rho_min <= c->rho_max && c->rho_max <= 1.0))
+    return fail(DMT_ERR_INVALID, "adaptation: need 0 <= rho_min <= rho_max <= 1");
+  if (c->until < 0) return fail(DMT_ERR_INVALID, "adaptation: until must be >= 0");
+  return DMT_OK;
+}
+
+// the numbers of the adaptation after iteration mcmciter (a positive multiple of c.every)
+static AdaptStep adapt_step(const dmt_adapt_config& c, int64_t mcmciter) {
+  const int64_t k = mcmciter / c.every;
+  const double delta = std::min(c.delta_max, c.delta0 / std::sqrt((double)k));
+  AdaptStep s;
+  s.k_up = std::exp(delta);
+  s.k_dn = std::exp(-delta);
+  s.n_lo = (int64_t)std::ceil(c.lo * (double)c.every);
+  s.n_hi = (int64_t)std::floor(c.hi * (double)c.every);
+  s.rho_min = c.rho_min;
+  s.rho_max = c.rho_max;
+  return s;
+}
+
+static dmt_status check_adapt_iter(const dmt_adapt_config* c, int64_t mcmciter) {
+  if (mcmciter < 1 || mcmciter % c->every != 0)
+    return fail(DMT_ERR_INVALID, "adaptation: mcmciter must be a positive multiple of every");
+  return DMT_OK;
+}
+
+dmt_status dmt_adapt_rule(const dmt_adapt_config* cfg, int64_t mcmciter, int64_t n,
+                          const double* rho_in, const int64_t* counts, double* rho_out,
+                          double* srho_out) {
+  DMT_TRY(check_adapt_config(cfg));
+  DMT_TRY(check_adapt_iter(cfg, mcmciter));
+  if (n < 0 || (n > 0 && (!rho_in || !counts || !rho_out)))
+    return fail(DMT_ERR_INVALID, "dmt_adapt_rule: null array or negative length");
+  for (int64_t j = 0; j < n; ++j)
+    if (!(rho_in[j] >= 0.0 && rho_in[j] <= 1.0)) return fail(DMT_ERR_INVALID, "rho outside [0,1]");
+  const bool ended = cfg->until > 0 && mcmciter > cfg->until;
+  const AdaptStep s = adapt_step(*cfg, mcmciter);
+  for (int64_t j = 0; j < n; ++j) {
+    double r = rho_in[j], sr = 0.0;
+    if (ended || !adapt_rule(s, counts[j], &r, &sr)) sr = std::sqrt(1.0 - r * r);
+    rho_out[j] = r;
+    if (srho_out) srho_out[j] = sr;
+  }
+  return DMT_OK;
+}
+
+dmt_status dmt_get_rho(dmt_ens* h, int32_t layout, int64_t b0, int64_t b1, double* rho_out) {
+  DMT_TRY(enter(h));
+  Layout* L;
+  DMT_TRY(get_layout(h, layout, &L));
+  DMT_TRY(check_range(L, b0, b1));
+  if (b1 > b0) {
+    if (!rho_out) return fail(DMT_ERR_INVALID, "null rho_out");
+    HIP_OK(hipMemcpyAsync(rho_out, L->d_rho + b0, (size_t)(b1 - b0) * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIP_OK(stream_wait(h));
+  return DMT_OK;
+}
+
+dmt_status dmt_set_rho(dmt_ens* h, int32_t layout, int64_t b0, int64_t b1, const double* rho) {
+  DMT_TRY(enter(h));
+  Layout* L;
+  DMT_TRY(get_layout(h, layout, &L));
+  DMT_TRY(check_range(L, b0, b1));
+  if (b1 == b0) return DMT_OK;
+  if (!rho) return fail(DMT_ERR_INVALID, "null rho");
+  const int64_t n = b1 - b0;
+  std::vector<double> srho(n);
+  for (int64_t j = 0; j < n; ++j) {
+    if (!(rho[j] >= 0.0 && rho[j] <= 1.0)) return fail(DMT_ERR_INVALID, "rho outside [0,1]");
+    srho[j] = std::sqrt(1.0 - rho[j] * rho[j]);  // as build_layout
+  }
+  HIP_OK(hipMemcpyAsync(L->d_rho + b0, rho, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(L->d_srho + b0, srho.data(), (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+  HIP_OK(launch_sync_binfo_rho(L->d_binfo, L->d_rho, L->d_srho, b0, b1, h->stream));
+  HIP_OK(stream_wait(h));  // the host arrays are borrowed for the call only
+  return DMT_OK;
+}
+
+static dmt_status check_hist_window(const Layout* L, int64_t i0, int64_t i1) {
+  if (L->hist_len <= 0) return fail(DMT_ERR_STATE, "layout has no histories (ll_hist_len = 0)");
+  if (i0 < 1 || i1 < i0 || i1 > L->hist_len)
+    return fail(DMT_ERR_INVALID, "iterations " + std::to_string(i0) + ":" + std::to_string(i1) +
+                                     " outside 1:ll_hist_len");
+  return DMT_OK;
+}
+
+dmt_status dmt_accept_counts(dmt_ens* h, int32_t layout, int64_t b0, int64_t b1, int64_t i0,
+                             int64_t i1, int64_t* counts_out) {
+  DMT_TRY(enter(h));
+  Layout* L;
+  DMT_TRY(get_layout(h, layout, &L));
+  DMT_TRY(check_range(L, b0, b1));
+  DMT_TRY(check_hist_window(L, i0, i1));
+  if (b1 == b0) return DMT_OK;
+  if (!counts_out) return fail(DMT_ERR_INVALID, "null counts_out");
+  DMT_TRY(ensure_stage(h, b1 - b0));
+  AdaptArgs a{};
+  a.b0 = b0, a.b1 = b1, a.nblocks = L->nblocks;
+  a.acc_hist = L->d_acch;
+  a.i0 = i0, a.i1 = i1;
+  a.counts = reinterpret_cast<int64_t*>(h->d_stage);
+  HIP_OK(launch_accept_counts(a, h->stream));
+  HIP_OK(hipMemcpyAsync(counts_out, a.counts, (size_t)(b1 - b0) * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(stream_wait(h));
+  return DMT_OK;
+}
+
+// dmt_adapt_rho after enter(): queued on the stream; the host waits only to read n_changed
+static dmt_status adapt_rho_impl(dmt_ens* h, Layout* L, int64_t b0, int64_t b1, int64_t mcmciter,
+                                 const dmt_adapt_config* cfg, int64_t* n_changed) {
+  DMT_TRY(check_range(L, b0, b1));
+  DMT_TRY(check_adapt_config(cfg));
+  DMT_TRY(check_adapt_iter(cfg, mcmciter));
+  DMT_TRY(check_hist_window(L, mcmciter - cfg->every + 1, mcmciter));
+  if (n_changed) *n_changed = 0;
+  if (b1 == b0 || (cfg->until > 0 && mcmciter > cfg->until)) return DMT_OK;
+  AdaptArgs a{};
+  a.b0 = b0, a.b1 = b1, a.nblocks = L->nblocks;
+  a.acc_hist = L->d_acch;
+  a.i0 = mcmciter - cfg->every + 1, a.i1 = mcmciter;
+  a.step = adapt_step(*cfg, mcmciter);
+  a.rho = L->d_rho;
+  a.srho = L->d_srho;
+  a.binfo = L->d_binfo;
+  a.n_changed = L->d_nadapt;
+  HIP_OK(hipMemsetAsync(L->d_nadapt, 0, 4, h->stream));
+  HIP_OK(launch_adapt_rho(a, h->stream));
+  if (n_changed) {
+    uint32_t nc = 0;
+    HIP_OK(hipMemcpyAsync(&nc, L->d_nadapt, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(stream_wait(h));
+    *n_changed = (int64_t)nc;
+  }
+  return DMT_OK;
+}
+
+dmt_status dmt_adapt_rho(dmt_ens* h, int32_t layout, int64_t b0, int64_t b1, int64_t mcmciter,
+                         const dmt_adapt_config* cfg, int64_t* n_changed) {
+  DMT_TRY(enter(h));
+  Layout* L;
+  DMT_TRY(get_layout(h, layout, &L));
+  return adapt_rho_impl(h, L, b0, b1, mcmciter, cfg, n_changed);
+}
+
+dmt_status dmt_set_run_adaptation(dmt_ens* h, int32_t layout, const dmt_adapt_config* cfg) {
+  DMT_TRY(enter(h));
+  Layout* L;
+  DMT_TRY(get_layout(h, layout, &L));
+  if (!cfg || cfg->every == 0) {
+    L->adapt = dmt_adapt_config{};
+    return DMT_OK;
+  }
+  DMT_TRY(check_adapt_config(cfg));
+  if (L->hist_len <= 0) return fail(DMT_ERR_STATE, "layout has no histories (ll_hist_len = 0)");
+  L->adapt = *cfg;
+  return DMT_OK;
+}
+
 dmt_status dmt_set_run_snapshots(dmt_ens* h, int64_t every, int64_t slot0) {
   DMT_TRY(enter(h));
   if (every < 0) return fail(DMT_ERR_INVALID, "every must be >= 0");
@@ -1662,26 +1832,41 @@ static dmt_status mcmc_run_impl(dmt_ens* h, int32_t layout, int64_t b0, int64_t 
   if (n_iter == 0) return DMT_OK;
   if (L->hist_len > 0 && iter0 + n_iter - 1 > L->hist_len)
     return fail(DMT_ERR_INVALID, "iterations outside 1:ll_hist_len");
-  if (h->run_snap_every > 0) {
+  if (h->run_snap_every > 0 || L->adapt.every > 0) {
     // snapshots inside the run (the smoothing loop's `deepcopy(sp.u.XX)` every k iterations,
-    // docs/src/tutorials/biblock/smoothing.md:40-44): the run is cut after every iteration
-    // k ≡ 0 mod every and u is snapshotted there, stream-ordered (no host round trip); the
-    // pieces take the same stream keys as one run (auto keys: consecutive counter values)
-    const int64_t every = h->run_snap_every;
+    // docs/src/tutorials/biblock/smoothing.md:40-44) and adaptation of ρ (dmt_set_run_adaptation):
+    // one cut loop serves both.  The run is cut after every iteration that is a multiple of
+    // either `every` (adaptation: up to its `until`); there u is snapshotted if due, then ρ of
+    // the run's range adapted if due, stream-ordered; the pieces take the same stream keys as
+    // one run (auto keys: consecutive counter values)
+    const int64_t snap_every = h->run_snap_every;
+    const dmt_adapt_config ad = L->adapt;
     h->run_snap_every = 0;
+    L->adapt.every = 0;
+    // next multiple of `every` that is >= it
+    auto next_cut = [](int64_t it, int64_t every) { return ((it + every - 1) / every) * every; };
+    auto adapts_at = [&ad](int64_t i) {
+      return ad.every > 0 && i % ad.every == 0 && (ad.until == 0 || i <= ad.until);
+    };
     dmt_status st = DMT_OK;
     for (int64_t done = 0; done < n_iter && st == DMT_OK;) {
       const int64_t it = iter0 + done;
-      const int64_t k = ((it + every - 1) / every) * every;  // next snapshot iteration >= it
-      const int64_t n = std::min(n_iter - done, k - it + 1);
+      int64_t n = n_iter - done;
+      if (snap_every > 0) n = std::min(n, next_cut(it, snap_every) - it + 1);
+      if (ad.every > 0 && adapts_at(next_cut(it, ad.every)))
+        n = std::min(n, next_cut(it, ad.every) - it + 1);
       st = mcmc_run_impl(h, layout, b0, b1, it, n, salt, out ? out + 3 * done : nullptr, global);
       done += n;
-      if (st == DMT_OK && (iter0 + done - 1) % every == 0) {
-        st = dmt_snapshot_take(h, DMT_U, h->run_snap_next, iter0 + done - 1);
+      const int64_t last = iter0 + done - 1;
+      if (st == DMT_OK && snap_every > 0 && last % snap_every == 0) {
+        st = dmt_snapshot_take(h, DMT_U, h->run_snap_next, last);
         h->run_snap_next = (h->run_snap_next + 1) % h->snap_slots;
       }
+      if (st == DMT_OK && adapts_at(last)) st = enter(h);
+      if (st == DMT_OK && adapts_at(last)) st = adapt_rho_impl(h, L, b0, b1, last, &ad, nullptr);
     }
-    h->run_snap_every = every;
+    h->run_snap_every = snap_every;
+    L->adapt = ad;
     return st;
   }
   // stream keys: iteration it draws its normals and its Exp(1) variables with key word

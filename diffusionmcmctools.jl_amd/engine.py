@@ -334,6 +334,44 @@ class Ensemble:
         (slots slot0, slot0 + 1, … of snapshot_reserve, a ring); every = 0: off."""
         L.call("dmt_set_run_snapshots", self._h, int(every), int(slot0))
 
+    # ---------------------------------------------------------------- pCN memory ρ
+    def get_rho(self, layout, b0, b1):
+        """bb.ρ of blocks [b0, b1) as the device holds it (src/biblock.jl:43-47)."""
+        out = np.empty(b1 - b0, dtype=np.float64)
+        L.call("dmt_get_rho", self._h, layout, b0, b1, L.f64p(out))
+        return out
+
+    def set_rho(self, layout, b0, b1, rho):
+        """bb.ρ = v for blocks [b0, b1) (a scalar or one value per block); histories, ll and
+        ll° stay."""
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(rho, dtype=np.float64), (b1 - b0,)))
+        L.call("dmt_set_rho", self._h, layout, b0, b1, L.f64p(v))
+
+    def accept_counts(self, layout, b0, b1, i0, i1):
+        """Per block: accepted iterations among i0..i1 (1-based, inclusive), summed on the
+        device (no history download)."""
+        out = np.empty(b1 - b0, dtype=np.int64)
+        L.call("dmt_accept_counts", self._h, layout, b0, b1, int(i0), int(i1),
+               out.ctypes.data_as(C.POINTER(C.c_int64)))
+        return out
+
+    def adapt_rho(self, layout, b0, b1, mcmciter, cfg, want_changed=True):
+        """One adaptation of ρ of blocks [b0, b1) after iteration ``mcmciter`` (a positive
+        multiple of ``cfg["every"]``) by the rule of include/dmt.h; ``cfg``: :func:`adapt_config`.
+        Returns the number of blocks whose ρ changed (``want_changed=False``: None, and the
+        call does not wait for the device)."""
+        c = _adapt_struct(cfg)
+        n = C.c_int64()
+        L.call("dmt_adapt_rho", self._h, layout, b0, b1, int(mcmciter), C.byref(c),
+               C.byref(n) if want_changed else None)
+        return n.value if want_changed else None
+
+    def set_run_adaptation(self, layout, cfg):
+        """Adapt ρ inside every later mcmc_run of ``layout`` after each iteration i with
+        i % every == 0 (and i <= until); ``cfg`` None (or every = 0): off."""
+        c = None if cfg is None else _adapt_struct(cfg)
+        L.call("dmt_set_run_adaptation", self._h, layout, None if c is None else C.byref(c))
+
     # ---------------------------------------------------------------- misc
     def sync(self):
         st = L.fast["dmt_sync"](self._h)
@@ -437,6 +475,39 @@ class LazyFlags:
 
     def __repr__(self):
         return f"LazyFlags({self._get()!r})"
+
+
+ADAPT_FIELDS = ("every", "lo", "hi", "delta0", "delta_max", "rho_min", "rho_max", "until")
+
+
+def adapt_config(every, lo=0.15, hi=0.35, delta0=0.5, delta_max=0.5, rho_min=0.01,
+                 rho_max=0.9999, until=0):
+    """The adaptation config of include/dmt.h (dmt_adapt_config) as a dict: after every
+    ``every``-th iteration a block whose acceptance rate over the last ``every`` iterations is
+    below ``lo`` moves logit ρ up by δ = min(delta_max, delta0 / √k) (k-th adaptation), above
+    ``hi`` down by δ, clamped to [rho_min, rho_max]; ``until`` > 0 ends adaptation after that
+    iteration.  The default band brackets the 0.234 of random-walk proposals."""
+    return dict(every=int(every), lo=float(lo), hi=float(hi), delta0=float(delta0),
+                delta_max=float(delta_max), rho_min=float(rho_min), rho_max=float(rho_max),
+                until=int(until))
+
+
+def _adapt_struct(cfg):
+    return L.dmt_adapt_config(*(cfg[k] for k in ADAPT_FIELDS))
+
+
+def adapt_rule(cfg, mcmciter, rho, counts):
+    """The adaptation rule on host arrays (dmt_adapt_rule; no device): returns (ρ', sqrt(1 − ρ'²))
+    for ρ ``rho`` and window counts ``counts`` after iteration ``mcmciter``."""
+    r = np.ascontiguousarray(rho, dtype=np.float64).ravel()
+    c = np.ascontiguousarray(counts, dtype=np.int64).ravel()
+    if r.size != c.size:
+        raise ValueError("one count per rho")
+    out, sout = np.empty_like(r), np.empty_like(r)
+    s = _adapt_struct(cfg)
+    L.call("dmt_adapt_rule", C.byref(s), int(mcmciter), r.size, L.f64p(r),
+           c.ctypes.data_as(C.POINTER(C.c_int64)), L.f64p(out), L.f64p(sout))
+    return out, sout
 
 
 def comm_unique_id() -> bytes:

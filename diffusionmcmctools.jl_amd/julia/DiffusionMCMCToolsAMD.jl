@@ -38,7 +38,7 @@ import DiffusionMCMCTools: draw_proposal_path!, accept_reject_proposal_path!, lo
 export DeviceSamplingEnsemble, DeviceSamplingPair, DeviceSamplingUnit, DeviceBlockEnsemble,
     DeviceBlockCollection, DeviceBiBlock, DeviceBlock, use_device!, mcmc_step!, mcmc_run!,
     download_XX, download_WW, upload_obs!, snapshot_every!, law_record, guiding_linear, sync,
-    upload_aux!, upload_aux_a!, device_model, device_aux
+    upload_aux!, upload_aux_a!, device_model, device_aux, adapt_ρ!, set_run_adaptation!
 
 const libdmt = get(ENV, "DMT_LIB", joinpath(@__DIR__, "..", "libdmt.so"))
 
@@ -77,6 +77,18 @@ struct dmt_config
     device::Int32
     grid_shared::Int32
     mapping::Int32
+end
+
+# the adaptation of the pCN memory ρ (include/dmt.h, "pCN memory ρ")
+struct dmt_adapt_config
+    every::Int64
+    lo::Float64
+    hi::Float64
+    delta0::Float64
+    delta_max::Float64
+    rho_min::Float64
+    rho_max::Float64
+    until::Int64
 end
 
 function check(st::Int32)
@@ -818,7 +830,78 @@ end
 function Base.getproperty(bb::DeviceBiBlock, s::Symbol)
     s === :b && return DeviceBlock(bb, DMT_U)
     s === :b° && return DeviceBlock(bb, DMT_UPROP)
+    s === :ρ && return _rho(bb)[1]   # the device's value (the field keeps the constructor's)
     getfield(bb, s)
+end
+
+# bb.ρ = v (the reference's BiBlock is a mutable struct with a plain ρ field,
+# src/biblock.jl:43-47): written to the device, the next draw uses it
+function Base.setproperty!(bb::DeviceBiBlock, s::Symbol, v)
+    s === :ρ || error("DeviceBiBlock: only ρ can be assigned")
+    _set_rho!(bb, v)
+    v
+end
+
+function _rho(x::DeviceBlocks)
+    out = Vector{Float64}(undef, _n(x))
+    check(ccall((:dmt_get_rho, libdmt), Int32, (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Float64}),
+                getfield(x, :se).h, getfield(x, :layout), getfield(x, :b0), getfield(x, :b1), out))
+    out
+end
+
+function _set_rho!(x::DeviceBlocks, v)
+    vals = Vector{Float64}(undef, _n(x))
+    vals .= v
+    check(ccall((:dmt_set_rho, libdmt), Int32, (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Float64}),
+                getfield(x, :se).h, getfield(x, :layout), getfield(x, :b0), getfield(x, :b1), vals))
+end
+
+# ρ of every block of a collection / an ensemble, read from and written to the device
+function Base.getproperty(x::Union{DeviceBlockCollection,DeviceBlockEnsemble}, s::Symbol)
+    s === :ρ && return _rho(x)
+    getfield(x, s)
+end
+function Base.setproperty!(x::Union{DeviceBlockCollection,DeviceBlockEnsemble}, s::Symbol, v)
+    s === :ρ || error("only ρ can be assigned")
+    _set_rho!(x, v)
+    v
+end
+
+_adapt_config(every; accept_band=(0.15, 0.35), delta0=0.5, delta_max=0.5,
+              rho_bounds=(0.01, 0.9999), until=0) =
+    dmt_adapt_config(every, accept_band[1], accept_band[2], delta0, delta_max, rho_bounds[1],
+                     rho_bounds[2], until)
+
+"""
+    adapt_ρ!(x, mcmciter; every=mcmciter, accept_band, delta0, delta_max, rho_bounds, until)
+
+One adaptation of every block's ρ after iteration `mcmciter` from its own acceptance count over
+the last `every` iterations — what a caller of the reference does by hand with
+`accpt_rate(bb, range)` (src/biblock.jl:232) and `bb.ρ = …` (src/biblock.jl:43-47), here on the
+device for all blocks at once (include/dmt.h, "pCN memory ρ").  Returns the number of blocks
+whose ρ changed.  The two calls that take the config struct use `@ccall`.
+"""
+function adapt_ρ!(x::DeviceBlocks, mcmciter::Integer; every=mcmciter, kw...)
+    cfg = Ref(_adapt_config(every; kw...))
+    n = Ref{Int64}(0)
+    check(@ccall libdmt.dmt_adapt_rho(getfield(x, :se).h::Ptr{Cvoid}, getfield(x, :layout)::Int32,
+                                      getfield(x, :b0)::Int64, getfield(x, :b1)::Int64,
+                                      mcmciter::Int64, cfg::Ref{dmt_adapt_config},
+                                      n::Ref{Int64})::Int32)
+    n[]
+end
+
+"""
+    set_run_adaptation!(x, every; accept_band, delta0, delta_max, rho_bounds, until)
+
+Adapt ρ inside every later `mcmc_run!` of `x`'s layout after each iteration i with
+`i % every == 0` (and `i <= until` when given), without a host round trip; `every = 0`: off.
+"""
+function set_run_adaptation!(x::DeviceBlocks, every::Integer; kw...)
+    cfg = Ref(_adapt_config(every; kw...))
+    check(@ccall libdmt.dmt_set_run_adaptation(getfield(x, :se).h::Ptr{Cvoid},
+                                               getfield(x, :layout)::Int32,
+                                               cfg::Ref{dmt_adapt_config})::Int32)
 end
 
 _llsel(b::DeviceBlock) = getfield(b, :unit) == DMT_U ? DMT_BLK_LL : DMT_BLK_LLPROP
@@ -1266,6 +1349,18 @@ function ll_of_accepted(x::DeviceBlocks, i)
     llh = _hist(x, DMT_BLK_LL_HIST, Float64)[:, i]
     llph = _hist(x, DMT_BLK_LLPROP_HIST, Float64)[:, i]
     v = ifelse.(acc, llph, llh)
+    x isa DeviceBiBlock ? v[1] : v
+end
+
+# a contiguous window: counted on the device (dmt_accept_counts), the history stays there
+function accpt_rate(x::DeviceBlocks, range::AbstractUnitRange{<:Integer})
+    isempty(range) && return invoke(accpt_rate, Tuple{DeviceBlocks,Any}, x, range)
+    counts = Vector{Int64}(undef, _n(x))
+    check(ccall((:dmt_accept_counts, libdmt), Int32,
+                (Ptr{Cvoid}, Int32, Int64, Int64, Int64, Int64, Ptr{Int64}),
+                getfield(x, :se).h, getfield(x, :layout), getfield(x, :b0), getfield(x, :b1),
+                first(range), last(range), counts))
+    v = counts ./ length(range)
     x isa DeviceBiBlock ? v[1] : v
 end
 

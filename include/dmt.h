@@ -512,6 +512,77 @@ dmt_status dmt_snapshot_download(dmt_ens* h, int32_t what, int64_t slot, double*
                                  int64_t* mcmciter);
 dmt_status dmt_snapshot_write(dmt_ens* h, const char* path, int64_t s0, int64_t s1);
 
+/* ---------------- pCN memory ρ: access and per-block adaptation ----------------
+ * The reference's BiBlock is a mutable struct with a plain field ρ::Float64 (src/biblock.jl:43-47):
+ * callers assign bb.ρ and tune it from accpt_rate(bb, range) (src/biblock.jl:232), the mean of
+ * accpt_history over a range of iterations.  Here ρ lives on the device; these calls read and
+ * write it, count the accepted iterations of a window per block without downloading the
+ * history, and adapt every block's ρ from its own count, also inside dmt_mcmc_run.
+ *
+ * The adaptation rule.  After iteration i = mcmciter (a positive multiple of `every`), with
+ *   k = i / every,  δ = min(delta_max, delta0 / sqrt(k))         (diminishing adaptation)
+ *   n_lo = ceil(lo·every),  n_hi = floor(hi·every)
+ *   c_b = Σ_{j = i−every+1 .. i} accpt_history[j][b]
+ * block b with c_b < n_lo takes κ = exp(δ) (too few accepts: more memory, smaller moves), with
+ * c_b > n_hi takes κ = exp(−δ), and otherwise keeps ρ_b and sqrt(1 − ρ_b²) bit for bit.  Then
+ *   num = κ·ρ,  ρ' = num / (num + (1 − ρ))     (= sigmoid(logit ρ ± δ) without a transcendental),
+ *   ρ' = min(max(ρ', rho_min), rho_max),
+ * all in fp64 with separately rounded *, +, /, sqrt (for fp32 ensembles too: ρ is stored as double
+ * and cast by the kernels), so the host function dmt_adapt_rule and the device give the same bits.
+ * ρ = 0 (the reference's default) and ρ = 1 are fixed points of the move: they leave only through
+ * the clamp to [rho_min, rho_max].  The rule is stateless — everything follows from i and the
+ * config — so a checkpoint needs nothing beyond ρ itself (dmt_get_rho / dmt_set_rho).  Once
+ * until > 0 and i > until, adaptation has ended and ρ stays.
+ * A config is valid when every >= 1, 0 <= lo <= hi <= 1, delta0 and delta_max are finite and
+ * > 0, 0 <= rho_min <= rho_max <= 1 and until >= 0 (else DMT_ERR_INVALID); the counts come from
+ * accpt_history, so a layout without histories gives DMT_ERR_STATE. */
+typedef struct {
+    int64_t every;          /* adapt after every iteration i with i % every == 0 */
+    double lo, hi;          /* the band of acceptance rates that leaves ρ alone */
+    double delta0;          /* logit step of the first adaptation */
+    double delta_max;       /* cap of the logit step */
+    double rho_min, rho_max;
+    int64_t until;          /* last adapting iteration; 0: no end */
+} dmt_adapt_config;
+
+/* bb.ρ of blocks [b0, b1) (src/biblock.jl:43-47), rho_out: double[b1-b0]. */
+dmt_status dmt_get_rho(dmt_ens* h, int32_t layout, int64_t b0, int64_t b1, double* rho_out);
+/* bb.ρ = v (the mutable field, src/biblock.jl:43-47) for blocks [b0, b1): 0 <= ρ <= 1 as
+ * dmt_create_layout asks; sqrt(1 − ρ²) is formed on the host, as there.  Histories, ll and ll°
+ * stay.  Later draws use the new value. */
+dmt_status dmt_set_rho(dmt_ens* h, int32_t layout, int64_t b0, int64_t b1, const double* rho);
+/* Per block of [b0, b1): the number of accepted iterations among i0..i1 (1-based, inclusive,
+ * within 1:hist_len) — accpt_rate(bb, i0:i1)·(i1 − i0 + 1) (src/biblock.jl:232), summed on the
+ * device.  counts_out: int64[b1-b0]. */
+dmt_status dmt_accept_counts(dmt_ens* h, int32_t layout, int64_t b0, int64_t b1, int64_t i0,
+                             int64_t i1, int64_t* counts_out);
+/* One adaptation of ρ of blocks [b0, b1) after iteration mcmciter by the rule above (the tuning
+ * a caller of the reference does by hand from accpt_rate, src/biblock.jl:232, and bb.ρ = …,
+ * src/biblock.jl:43-47).  DMT_ERR_INVALID unless mcmciter is a positive multiple of cfg->every
+ * and the window mcmciter−every+1 .. mcmciter lies in 1:hist_len.  With until passed it does
+ * nothing (n_changed = 0).  n_changed (nullable): the blocks whose ρ changed; reading it waits
+ * for the device, passing NULL does not.  Blocks outside [b0, b1) are not touched.  Rank-local:
+ * no collective. */
+dmt_status dmt_adapt_rho(dmt_ens* h, int32_t layout, int64_t b0, int64_t b1, int64_t mcmciter,
+                         const dmt_adapt_config* cfg, int64_t* n_changed);
+/* Adaptation inside dmt_mcmc_run / dmt_mcmc_run_local of this layout: from now on a run is cut
+ * after every iteration i with i % cfg->every == 0 (and i <= until) and dmt_adapt_rho(h, layout,
+ * b0, b1, i, cfg, NULL) of the run's own range is queued there, after the run snapshot of that
+ * iteration when one is due (dmt_set_run_snapshots) — the pieces take the same stream keys as an
+ * unsplit run, so the run equals the loop of shorter runs and dmt_adapt_rho calls.  Runs on
+ * other layouts are not affected.  cfg = NULL or every = 0 turns it off (the default).
+ * Under a communicator (dmt_comm_init) every rank must install the same config: the cuts decide
+ * the sequence of all-gathers the ranks issue.  The adaptation itself is per block and needs no
+ * collective, so a sharded ensemble adapts exactly as the unsharded one. */
+dmt_status dmt_set_run_adaptation(dmt_ens* h, int32_t layout, const dmt_adapt_config* cfg);
+/* The rule of dmt_adapt_rho on host arrays (no device needed): rho_out[j] (and srho_out[j] =
+ * sqrt(1 − rho_out[j]²), nullable) from rho_in[j] in [0, 1] and the window count counts[j],
+ * j < n, after iteration mcmciter (src/biblock.jl:43-47,232 as above).  rho_out may alias
+ * rho_in. */
+dmt_status dmt_adapt_rule(const dmt_adapt_config* cfg, int64_t mcmciter, int64_t n,
+                          const double* rho_in, const int64_t* counts, double* rho_out,
+                          double* srho_out);
+
 /* ---------------- random stream counter (DMT_RNG_AUTO) ---------------- */
 dmt_status dmt_rng_counter(dmt_ens* h, uint64_t* next);
 dmt_status dmt_set_rng_counter(dmt_ens* h, uint64_t next);
