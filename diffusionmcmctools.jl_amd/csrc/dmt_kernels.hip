@@ -25,6 +25,7 @@
 #include "dmt_device.h"
 #include "dmt_internal.h"
 #include "dmt_filter.h"
+#include "dmt_tuning.h"
 
 // gfx950 only: no other target is built or validated (the persistent kernels' inter-workgroup
 // hand-offs use gfx950's write-through agent-scope stores).
@@ -34,15 +35,12 @@
 
 namespace dmt {
 
-#ifndef DMT_SPLIT  // 1: one translation unit of the split build (Makefile; see DMT_DISPATCH)
-#define DMT_SPLIT 0
+// One translation unit of seven (Makefile; see DMT_DISPATCH): a (precision, model) group's
+// kernels and entry points, or the model-independent kernels and launchers.
+#if !defined(DMT_TU_GROUP) || DMT_TU_GROUP < -1 || DMT_TU_GROUP > 5
+#error "dmt_kernels.hip: compile with -DDMT_TU_GROUP=0..5 (a model group) or -1 (the common unit)"
 #endif
-#ifndef DMT_TU_GROUP
-#define DMT_TU_GROUP -1
-#endif
-// the model-independent kernels and launchers: the monolithic build, or the split build's
-// common unit
-#define DMT_TU_COMMON (!DMT_SPLIT || DMT_TU_GROUP < 0)
+#define DMT_TU_COMMON (DMT_TU_GROUP < 0)
 
 template <int K>
 struct Log2 { static constexpr int v = K == 1 ? 0 : 1 + Log2<(K > 1 ? K / 2 : 1)>::v; };
@@ -65,20 +63,10 @@ __device__ __forceinline__ T tree_sum(T* v) {
 // the values are the same.  Measured (profiles/r03f, one box): non-temporal X°/W° stores take
 // C3 (fp64) from 1 239 to 1 144 µs per draw, but C5 (fp32, whose mixed-selector stores write
 // partial lines) from 1 878 to 1 957 µs; non-temporal loads slow both (1 414, 2 291 µs).  So:
-// NT stores for fp64 (DMT_LANE_NT_STORES=1 also for fp32, 0 for none), normal loads.
-#ifndef DMT_LANE_NT_LOADS
-#define DMT_LANE_NT_LOADS 0
-#endif
-#ifndef DMT_LANE_NT_STORES
-#define DMT_LANE_NT_STORES 2  // 2: fp64 only, 1: all, 0: none
-#endif
+// NT stores for fp64 (DMT_LANE_NT_STORES, dmt_tuning.h), normal loads.
 template <class T>
 __device__ __forceinline__ T lane_ld(const T* p) {
-#if DMT_LANE_NT_LOADS
-  return __builtin_nontemporal_load(p);
-#else
   return *p;
-#endif
 }
 template <class T>
 __device__ __forceinline__ void lane_st(T* p, T v) {
@@ -94,14 +82,8 @@ __device__ __forceinline__ void lane_st(T* p, T v) {
 // a branch, so the waitcnt pass can count outstanding loads exactly).  Normals of a chunk
 // come in whole Box–Muller pairs (K·M even); the chunk's K Girsanov terms are summed as an
 // aligned subtree and inserted into the 64-step pairwise counter.  A tail of < K steps
-// runs through the single-step path.
-#ifndef DMT_LANE_AHEAD  // lane kernels (row layout): chunks of K steps loaded ahead (1 or 2;
-#define DMT_LANE_AHEAD 0  // 0: two when a chunk's inputs fit in 40 registers per lane, e.g. FHN)
-#endif
-#ifndef DMT_KCHUNK_PAIR_BASE
-#define DMT_KCHUNK_PAIR_BASE 4  // pair-kernel chunk (doubled when it would hold an odd number of
-                                // Philox blocks: Lorenz fp32, 3 normals per step → 8 steps)
-#endif
+// runs through the single-step path.  DMT_LANE_AHEAD (dmt_tuning.h): one or two chunks ahead.
+//
 // Two lanes of one wave (l and l + 32) holding the same recording (the pair mapping,
 // k_block_pair): role 0 draws the even Philox blocks of a chunk, role 1 the odd ones, and
 // v_permlane32_swap hands each half's normals to the other — both roles then run the same
@@ -167,11 +149,7 @@ __device__ __forceinline__ bool run_segment(const Law<Mdl, T>& L, const T* __res
   // W planes hold increments: row 0 = W(t0), row i+1 = dW_i
   const int nst = np - 1;
   // wave-uniform: every active lane's law has σ = I (the step's fast path)
-#ifdef DMT_NO_UNIT_FAST  // measurement variant: the generic path (per-lane selects) always
-  const bool all_unit = false;
-#else
   const bool all_unit = !Mdl::kLinear && __ballot(L.unit) == __ballot(1);
-#endif
   T tcur = tb[0];
   if (cpx) {
 #pragma unroll
@@ -189,12 +167,6 @@ __device__ __forceinline__ bool run_segment(const Law<Mdl, T>& L, const T* __res
   }
   PSum<T> ps;
   ps.init();
-#ifdef DMT_PROBE_PKT  // timing probe only: a chunk's X°/W° rows as per-lane K-step packets
-  constexpr bool PKT = MODE == MODE_PCN && !PAIR;
-#else
-  constexpr bool PKT = false;
-#endif
-  T pkx[K][D], pkw[K][M];
 
   struct Chunk {
     T t[K], H[K][HP], F[K][D], W[K][M], Z[K][M], Xu[K][D];
@@ -221,7 +193,7 @@ __device__ __forceinline__ bool run_segment(const Law<Mdl, T>& L, const T* __res
   };
   // one Euler step from registers; returns the Girsanov term G·dt
   auto step = [&](int i, T tn, const T* Hi, const T* Fi, const T* Wi, const T* Zi,
-                  const T* Xui, const int pj) -> T {
+                  const T* Xui) -> T {
     const T dt = tn - tcur;
     T dW[M];
     if (cpx) {
@@ -237,8 +209,7 @@ __device__ __forceinline__ bool run_segment(const Law<Mdl, T>& L, const T* __res
       for (int k = 0; k < M; ++k) {
         if (cpw) lane_st(&Wcdb[((int64_t)(i + 1) * M + k) * kLanes], Wi[k]);
         dW[k] = dfma(rho, Wi[k], srho * (sdt * Zi[k]));
-        if (PKT && pj >= 0) pkw[pj][k] = dW[k];
-        else lane_st(&Wdb[((int64_t)(i + 1) * M + k) * kLanes], dW[k]);
+        lane_st(&Wdb[((int64_t)(i + 1) * M + k) * kLanes], dW[k]);
       }
     }
     T r[D], b[D], sdW[D], Mg[D * D], cg[D];
@@ -271,10 +242,7 @@ __device__ __forceinline__ bool run_segment(const Law<Mdl, T>& L, const T* __res
     }
     euler_step<Mdl, T>(L.th, Mg, cg, b, dt, sdW, x);
 #pragma unroll
-    for (int p = 0; p < D; ++p) {
-      if (PKT && pj >= 0) pkx[pj][p] = x[p];
-      else lane_st(&Xdb[((int64_t)(i + 1) * D + p) * kLanes], x[p]);
-    }
+    for (int p = 0; p < D; ++p) lane_st(&Xdb[((int64_t)(i + 1) * D + p) * kLanes], x[p]);
     tcur = tn;
     // recompute_path!(…; skip): the segment's last ll_skip steps add no term
     return (MODE == MODE_RECOMPUTE && i >= nst - ll_skip) ? (T)0 : G * dt;
@@ -316,35 +284,8 @@ __device__ __forceinline__ bool run_segment(const Law<Mdl, T>& L, const T* __res
     T gv[K];
 #pragma unroll
     for (int j = 0; j < K; ++j)
-      gv[j] = step(c0 + j, cur.t[j], cur.H[j], cur.F[j], cur.W[j], cur.Z[j], cur.Xu[j], j);
+      gv[j] = step(c0 + j, cur.t[j], cur.H[j], cur.F[j], cur.W[j], cur.Z[j], cur.Xu[j]);
     ps.template add_subtree<Log2<K>::v>(tree_sum<T, K>(gv));
-    if constexpr (PKT) {
-      static_assert(K * sizeof(T) % 16 == 0, "packets of whole 16-byte pieces");
-      typedef T v16 __attribute__((ext_vector_type(16 / sizeof(T))));
-      constexpr int NV = 16 / sizeof(T);
-#pragma unroll
-      for (int p = 0; p < D; ++p) {
-        T* q = Xd + (row + c0 + 1) * D * kLanes + ((int64_t)p * kLanes + lane) * K;
-#pragma unroll
-        for (int h = 0; h < K / NV; ++h) {
-          v16 v;
-#pragma unroll
-          for (int e = 0; e < NV; ++e) v[e] = pkx[h * NV + e][p];
-          __builtin_nontemporal_store(v, (v16*)(q + h * NV));
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < M; ++k) {
-        T* q = Wd + (row + c0 + 1) * M * kLanes + ((int64_t)k * kLanes + lane) * K;
-#pragma unroll
-        for (int h = 0; h < K / NV; ++h) {
-          v16 v;
-#pragma unroll
-          for (int e = 0; e < NV; ++e) v[e] = pkw[h * NV + e][k];
-          __builtin_nontemporal_store(v, (v16*)(q + h * NV));
-        }
-      }
-    }
   };
   // chunks in flight: one, or two where a chunk's inputs (t, H, F, W, Z, u.X: one value each)
   // take few registers — C3 (FHN, fp64): 1 061-1 070 -> 1 011-1 013 µs per draw; Lorenz's
@@ -396,7 +337,7 @@ __device__ __forceinline__ bool run_segment(const Law<Mdl, T>& L, const T* __res
       Wi[k] = READW ? lane_ld(&Wsb[((q + 1) * M + k) * kLanes]) : (T)0;
       Zi[k] = DRAW ? (PARITY ? (T)Zg[q * M + k] : ns.get((uint32_t)(i * M + k))) : (T)0;
     }
-    ps.add(step(i, tb[(q + 1) * tst], Hi, Fi, Wi, Zi, Xui, -1));
+    ps.add(step(i, tb[(q + 1) * tst], Hi, Fi, Wi, Zi, Xui));
   }
   sl = ps.finish();
   bool ok = isfinite(sl);
@@ -560,11 +501,12 @@ struct PairChunk {  // steps per chunk: an even number of whole Philox blocks of
 };
 
 // ---- MAP_LANE with lane packets (fp32 ensembles, BlockArgs::pk = kPathPacket).
-// The path planes X, W hold each lane's PK consecutive points of a component as one 64-byte
-// piece (plane_ix), so the per-lane buffers of u and u° (two, selected per segment exactly as
-// the reference swaps its containers) never share a piece of memory: a wave whose lanes hold u
-// in different buffers reads and writes whole pieces of its own, with no partial lines, no
-// consolidation copies and no third buffer (the row layout's path_plan).  FAST (every active
+// The path planes X, W hold each lane's kPathPacket = 32 consecutive points of a component as one
+// 128-byte packet (plane_ix), staged here in pieces of PK = 16 points, so the per-lane buffers
+// of u and u° (two, selected per segment exactly as the reference swaps its containers) never
+// share a piece of memory: a wave whose lanes hold u in different buffers reads and writes
+// whole pieces of its own, with no partial lines, no consolidation copies and no third buffer
+// (the row layout's path_plan).  FAST (every active
 // lane's segment starts at point ≡ PK − 1 of a packet, which dmt_create arranges for the first
 // segment of every recording): per packet of PK steps the lane loads u.W's packet one packet
 // ahead (NV 16-byte pieces per component, back to back) and stores the packet's X°, W° whole at
@@ -572,19 +514,6 @@ struct PairChunk {  // steps per chunk: an even number of whole Philox blocks of
 // plane_ix.  The arithmetic, its order and the Girsanov summation tree (K-step subtrees from
 // the segment start, single steps for the last nst % K) are run_segment's, so the results are
 // bit-identical to the row layout's and to the oracle's.
-#ifndef DMT_PK_ROLL  // 1: u.W's next packet loaded piece by piece into the registers just consumed
-#define DMT_PK_ROLL 1   // 0: the whole next packet in a second register set
-#endif
-#ifndef DMT_PK_SDT_TABLE  // shared grids: the packet kernel reads √dt from a per-point table
-#define DMT_PK_SDT_TABLE 1
-#endif
-#ifndef DMT_PK_CHUNK_STORE  // 1: X°, W° pieces stored at the end of the chunk that completes them
-#define DMT_PK_CHUNK_STORE 0   // (measured slower: C5 1 906-1 925 vs 1 432-1 449 µs per draw,
-                               // profiles/r05b) 0: the whole packet staged in registers, stored at its end
-#endif
-#ifndef DMT_PK_LDS  // 1: the packet's X°, W° staged in the lane's LDS rows
-#define DMT_PK_LDS 0   // 0: staged in registers (measured faster in the kernel: 1 455 vs 1 574 µs, C5)
-#endif
 // PAIR (k_block_pk_pair): two lanes (roles) of a wave per recording, l and l + 32 — each draws
 // every other Philox block of a chunk and the pair swaps halves (pair_exchange), both run the
 // recursion on the same values; role 0 stores X°, role 1 W° (every load is the same address
@@ -601,7 +530,7 @@ __device__ __forceinline__ bool run_segment_pk(const Law<Mdl, T>& L, const T* __
                                                NormalStream<T>& ns, const int64_t tq,
                                                const int64_t q0, const int np, const int lane,
                                                const T rho, const T srho, const int ll_skip,
-                                               T* x, T& sl, T* stg, const int role = 0,
+                                               T* x, T& sl, const int role = 0,
                                                const T* __restrict__ sdtab = nullptr) {
   constexpr int D = Mdl::D, M = Mdl::M, HP = D * (D + 1) / 2;
   constexpr bool DRAW = MODE != MODE_RECOMPUTE;
@@ -628,11 +557,7 @@ __device__ __forceinline__ bool run_segment_pk(const Law<Mdl, T>& L, const T* __
   const T* Ab = (TD && At) ? At + row * CA * kLanes + lane : nullptr;
   const bool td = TD && Ab != nullptr && __ballot(L.auxtd) != 0;
   const int nst = np - 1;
-#ifdef DMT_NO_UNIT_FAST
-  const bool all_unit = false;
-#else
   const bool all_unit = !Mdl::kLinear && __ballot(L.unit) == __ballot(1);
-#endif
   T tcur = tb[0];
   if (stx) {
 #pragma unroll
@@ -745,9 +670,6 @@ __device__ __forceinline__ bool run_segment_pk(const Law<Mdl, T>& L, const T* __
       // packet j of a component: the segment's points j·PK + 1 … j·PK + PK, NV pieces
       auto wpk = [&](int j, int k) -> const v16* { return (const v16*)&Ws[pix((int64_t)j * PK + 1, k, M)]; };
       v16 wc[M][NV];
-#if !DMT_PK_ROLL
-      v16 wn[M][NV];
-#endif
       if (READW) {
 #pragma unroll
         for (int k = 0; k < M; ++k)
@@ -757,33 +679,13 @@ __device__ __forceinline__ bool run_segment_pk(const Law<Mdl, T>& L, const T* __
       Chunk cur, nxt;
       load(0, cur);
       for (int j = 0; j < npk; ++j) {
-#if !DMT_PK_ROLL
-        if (READW) {  // next packet (the tile's spare rows keep the last one in bounds)
-#pragma unroll
-          for (int k = 0; k < M; ++k)
-#pragma unroll
-            for (int v = 0; v < NV; ++v) wn[k][v] = wpk(j + 1, k)[v];
-        }
-#endif
         // the packet's X°, W° are collected step by step and leave as whole 16-byte pieces at
-        // the packet's end: in registers (default), or in the lane's LDS rows (stg[c][e][lane],
-        // a 65-element row pitch; DMT_PK_LDS=1 — faster in the layout probe, slower in the kernel)
+        // the packet's end, staged in registers
         // (a pair's roles each store one of the two, so they share NS staging rows: X° rows for
         // role 0, W° rows for role 1)
         constexpr int NS = PAIR ? (D > M ? D : M) : D + M, WR = PAIR ? 0 : D;
-#if DMT_PK_LDS
-        auto st = [&](int c, int e) -> T& { return stg[(c * PK + e) * 65 + lane]; };
-        auto put = [&](int c, int e, T v) { st(c, e) = v; };
-#elif DMT_PK_CHUNK_STORE
-        // a chunk of K steps completes K / VE whole pieces of every component: they leave at
-        // the chunk's end (the registers of one chunk's pieces instead of a whole packet's)
-        constexpr int CP = K / VE;
-        v16 ob[NS][CP];
-        auto put = [&](int c, int e, T v) { ob[c][(e % K) / VE][e % VE] = v; };
-#else
         v16 ob[NS][NV];
         auto put = [&](int c, int e, T v) { ob[c][e / VE][e % VE] = v; };
-#endif
 #pragma unroll
         for (int v = 0; v < PK / K; ++v) {
           const int c0 = j * PK + v * K;
@@ -810,25 +712,6 @@ __device__ __forceinline__ bool run_segment_pk(const Law<Mdl, T>& L, const T* __
               }
             }
           }
-#if !DMT_PK_LDS && DMT_PK_CHUNK_STORE
-          if (stx) {
-#pragma unroll
-            for (int p = 0; p < D; ++p) {
-              v16* dst = (v16*)&Xd[pix((int64_t)j * PK + 1, p, D)];
-#pragma unroll
-              for (int u = 0; u < CP; ++u) dst[v * CP + u] = ob[p][u];
-            }
-          }
-          if (stw) {
-#pragma unroll
-            for (int k = 0; k < M; ++k) {
-              v16* dst = (v16*)&Wd[pix((int64_t)j * PK + 1, k, M)];
-#pragma unroll
-              for (int u = 0; u < CP; ++u) dst[v * CP + u] = ob[WR + k][u];
-            }
-          }
-#endif
-#if DMT_PK_ROLL
           // the piece of u.W this chunk consumed is refilled with the next packet's: a prefetch
           // distance of one packet in the registers of one (the tile's spare rows keep the
           // last packet's in bounds)
@@ -838,27 +721,15 @@ __device__ __forceinline__ bool run_segment_pk(const Law<Mdl, T>& L, const T* __
 #pragma unroll
               for (int pc = v * K / VE; pc < (v + 1) * K / VE; ++pc) wc[k][pc] = wpk(j + 1, k)[pc];
           }
-#endif
           ps.template add_subtree<Log2<K>::v>(tree_sum<T, K>(gv));
           cur = nxt;
         }
-#if DMT_PK_LDS || !DMT_PK_CHUNK_STORE
-        auto piece = [&](int c, int v) -> v16 {
-#if DMT_PK_LDS
-          v16 o;
-#pragma unroll
-          for (int u = 0; u < VE; ++u) o[u] = st(c, v * VE + u);
-          return o;
-#else
-          return ob[c][v];
-#endif
-        };
         if (stx) {
 #pragma unroll
           for (int p = 0; p < D; ++p) {
             v16* dst = (v16*)&Xd[pix((int64_t)j * PK + 1, p, D)];
 #pragma unroll
-            for (int v = 0; v < NV; ++v) dst[v] = piece(p, v);
+            for (int v = 0; v < NV; ++v) dst[v] = ob[p][v];
           }
         }
         if (stw) {
@@ -866,18 +737,9 @@ __device__ __forceinline__ bool run_segment_pk(const Law<Mdl, T>& L, const T* __
           for (int k = 0; k < M; ++k) {
             v16* dst = (v16*)&Wd[pix((int64_t)j * PK + 1, k, M)];
 #pragma unroll
-            for (int v = 0; v < NV; ++v) dst[v] = piece(WR + k, v);
+            for (int v = 0; v < NV; ++v) dst[v] = ob[WR + k][v];
           }
         }
-#endif
-#if !DMT_PK_ROLL
-        if (READW) {
-#pragma unroll
-          for (int k = 0; k < M; ++k)
-#pragma unroll
-            for (int v = 0; v < NV; ++v) wc[k][v] = wn[k][v];
-        }
-#endif
       }
       i0 = npk * PK;
     }
@@ -944,7 +806,7 @@ __device__ __forceinline__ bool run_segment_pk(const Law<Mdl, T>& L, const T* __
 template <class Mdl, class T, int MODE, bool PARITY, int K, bool TD, bool PAIR = false,
           bool SDT = false>
 __device__ __forceinline__ void lane_block_pk(const BlockArgs<T>& a, const int64_t tile,
-                                              const int64_t blk, const int lane, T* stg,
+                                              const int64_t blk, const int lane,
                                               const int role = 0) {
   constexpr int D = Mdl::D, HP = D * (D + 1) / 2, PK = kPkChunkPts;  // staged piece (points)
   const int64_t tq = a.tile_qoff[tile];
@@ -995,11 +857,11 @@ __device__ __forceinline__ void lane_block_pk(const BlockArgs<T>& a, const int64
         aligned ? run_segment_pk<Mdl, T, MODE, PARITY, K, TD, PK, true, PAIR, SDT>(
                       L, a.t, a.t_shared, a.H[ls][kind], a.H_shared[ls][kind], a.F[ls][kind],
                       a.aux[kind], Ws, Wd, Xd, Zg, ns, tq, q0, a.seg_np[g], lane, rho, srho,
-                      a.ll_skip, x, sl, stg, role, SDT ? a.sdt : nullptr)
+                      a.ll_skip, x, sl, role, SDT ? a.sdt : nullptr)
                 : run_segment_pk<Mdl, T, MODE, PARITY, K, TD, PK, false, PAIR>(
                       L, a.t, a.t_shared, a.H[ls][kind], a.H_shared[ls][kind], a.F[ls][kind],
                       a.aux[kind], Ws, Wd, Xd, Zg, ns, tq, q0, a.seg_np[g], lane, rho, srho,
-                      a.ll_skip, x, sl, stg, role);
+                      a.ll_skip, x, sl, role);
     if (!sok) { ok = false; break; }
     ll = ll + sl;
   }
@@ -1011,17 +873,15 @@ __device__ __forceinline__ void lane_block_pk(const BlockArgs<T>& a, const int64
 
 template <class Mdl, class T, int MODE, bool PARITY, int K, bool TD = false, bool SDT = false>
 __global__ __launch_bounds__(64) void k_block_pk(const BlockArgs<T> a) {
-  __shared__ T stg[DMT_PK_LDS ? (Mdl::D + Mdl::M) * kPkChunkPts * 65 : 1];  // X°, W° (DMT_PK_LDS)
   int64_t tile, blk;
   if (!map_block(a, tile, blk)) return;
-  lane_block_pk<Mdl, T, MODE, PARITY, K, TD, false, SDT>(a, tile, blk, threadIdx.x, stg);
+  lane_block_pk<Mdl, T, MODE, PARITY, K, TD, false, SDT>(a, tile, blk, threadIdx.x);
 }
 
 // lane pairs on the packet layout (device-RNG draws): two waves per (recording tile, block
 // index), 32 recordings each on lanes (l, l + 32) — the mapping of k_block_pair
 template <class Mdl, class T, int MODE, bool TD = false>
 __global__ __launch_bounds__(64) void k_block_pk_pair(const BlockArgs<T> a) {
-  __shared__ T stg[DMT_PK_LDS ? (Mdl::D + Mdl::M) * kPkChunkPts * 65 : 1];
   const int lane = threadIdx.x, role = lane >> 5;
   const int64_t wave = blockIdx.x, w2 = wave >> 1;
   const int slot = (int)(wave & 1) * 32 + (lane & 31);
@@ -1032,7 +892,7 @@ __global__ __launch_bounds__(64) void k_block_pk_pair(const BlockArgs<T> a) {
   if (r >= a.R) return;
   const int64_t blk = a.blk_off[r] + b;
   if (blk >= a.blk_off[r + 1] || blk < a.b0 || blk >= a.b1) return;
-  lane_block_pk<Mdl, T, MODE, false, PairChunk<Mdl, T>::v, TD, true>(a, tile, blk, slot, stg, role);
+  lane_block_pk<Mdl, T, MODE, false, PairChunk<Mdl, T>::v, TD, true>(a, tile, blk, slot, role);
 }
 
 // ---- MAP_LANE, pair mapping: two waves per (recording tile, block index), each
@@ -1069,16 +929,10 @@ __global__ __launch_bounds__(64) void k_block_pair(const BlockArgs<T> a) {
 // X° stores.  Each wave's instruction stream is about half the single-wave kernel's, which is
 // what bounds the lane mapping when the ensemble has fewer tiles than the chip has SIMDs (C5).
 // Same operations in the same order as k_block: bit-identical.
-#ifndef DMT_PS_CHUNK
-#define DMT_PS_CHUNK 16
-#endif
 constexpr int kPsChunk = DMT_PS_CHUNK;
-#ifndef DMT_PS_MINW
-#define DMT_PS_MINW 1  // 2 (with DMT_PS_CHUNK 8, no spills) measured no better: 1 877 vs 1 749–1 782 µs on C5
-#endif
 
 template <class Mdl, class T>
-__global__ __launch_bounds__(128, DMT_PS_MINW) void k_block_ps(const BlockArgs<T> a) {
+__global__ __launch_bounds__(128, 1) void k_block_ps(const BlockArgs<T> a) {
   constexpr int D = Mdl::D, M = Mdl::M, HP = D * (D + 1) / 2;
   constexpr int L = kPsChunk, K = 4;
   static_assert(L % K == 0 && (L * M) % 2 == 0, "chunk must hold whole normal pairs");
@@ -1332,31 +1186,6 @@ __global__ __launch_bounds__(128, DMT_PS_MINW) void k_block_ps(const BlockArgs<T
 // and the summation tree are run_segment_pk's (K-step subtrees for every whole chunk, single
 // steps after), so the results are bit-identical to k_block_pk's.  A wave whose segments are
 // not aligned runs lane_block_pk on the consumer wave alone.
-#ifndef DMT_PSPK_STUB
-#define DMT_PSPK_STUB 0
-#endif
-#ifndef DMT_PSPK_GLDS  // the consumer's H, F chunks by LDS-DMA (global_load_lds_dwordx4), ring of
-#define DMT_PSPK_GLDS 0   // DMT_PSPK_GLDS_SLOTS slots, one fewer chunks in flight (0: register ring);
-#endif                    // C5 1 282 (4 slots), 1 293 (5) vs 1 278 µs per draw (profiles/r06e)
-#ifndef DMT_PSPK_GLDS_SLOTS
-#define DMT_PSPK_GLDS_SLOTS 4
-#endif
-// One LDS-DMA wave-instruction: each lane's 16 bytes at gsrc land at the wave-uniform LDS byte
-// address lds_dst + 16·lane (M0 holds the base; saved and restored in the same statement, the
-// recipe of cdna_hip_programming.md §5.7).  hipcc does not count it: the caller waits with its
-// own s_waitcnt vmcnt before reading the bytes.
-__device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-               "s_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-#ifndef DMT_PSPK_PAIR  // whole 128-byte lines per lane: a packet's first piece waits in LDS;
-#define DMT_PSPK_PAIR 1   // C5 1 152 vs 1 278 µs per draw without (profiles/r06e)
-#endif
-#ifndef DMT_PSPK_RING  // the consumer's H, F register ring (chunks of K steps; 2 = one ahead;
-#define DMT_PSPK_RING 2   // 4, three ahead, measured the same: 1 350 vs 1 341-1 343 µs, r05l)
-#endif
 template <class Mdl, class T, int K, bool SDT>
 __global__ __launch_bounds__(128, 1) void k_block_ps_pk(const BlockArgs<T> a) {
   constexpr int D = Mdl::D, M = Mdl::M, HP = D * (D + 1) / 2, PK = kPkChunkPts;  // staged piece
@@ -1366,20 +1195,13 @@ __global__ __launch_bounds__(128, 1) void k_block_ps_pk(const BlockArgs<T> a) {
   typedef T v16 __attribute__((ext_vector_type(VE)));
   __shared__ T s_dt[2][PK][64];
   __shared__ T s_dw[2][PK][M][64];
-  // the one-wave fallback's X°, W° staging (DMT_PK_LDS builds; one element otherwise)
-  __shared__ T stg[DMT_PK_LDS ? (Mdl::D + Mdl::M) * kPkChunkPts * 65 : 1];
-  // whole-line stores (DMT_PSPK_PAIR): a layout packet is kPathPacket / PK pieces; the first
+  // whole-line stores: a layout packet is kPathPacket / PK pieces; the first
   // piece of each waits in LDS (each lane its own slots) until the second completes the lane's
   // 128-byte line, which then leaves in one run of stores — a half line written ≈ 16 steps
   // before its other half was often evicted in between: a partial write, read back (FETCH)
-  constexpr bool PAIRW = DMT_PSPK_PAIR && kPathPacket == 2 * PK;
+  constexpr bool PAIRW = kPathPacket == 2 * PK;
   __shared__ v16 stW[PAIRW ? M : 1][PAIRW ? NV : 1][64];  // producer: W° first halves
   __shared__ v16 stX[PAIRW ? D : 1][PAIRW ? NV : 1][64];  // consumer: X° first halves
-  // the consumer's H, F chunks of K steps by LDS-DMA (DMT_PSPK_GLDS): slot image = the tile's
-  // rows as they lie in memory, H [K][HP][64] then F [K][D][64]
-  constexpr int GCH = K * HP * 64, GCF = K * D * 64;  // elements per chunk
-  constexpr int NGS = DMT_PSPK_GLDS ? DMT_PSPK_GLDS_SLOTS : 1;
-  [[maybe_unused]] __shared__ T hfr[NGS][DMT_PSPK_GLDS ? GCH + GCF : 1];
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int64_t tile = a.tile0 + blockIdx.x / a.MB;
@@ -1396,16 +1218,9 @@ __global__ __launch_bounds__(128, 1) void k_block_ps_pk(const BlockArgs<T> a) {
   const int g = act ? a.gfirst[blk] : 0;  // the block's only segment (host-checked)
   const int64_t q0 = act ? a.seg_q[g] : 0;
   const int64_t row = tq + q0;
-  // both waves take the same branch (same lanes, same values).  The LDS-DMA consumer
-  // (DMT_PSPK_GLDS) also needs every lane's segment at the tile's first row and per-point H
-  bool glds_off = false;
-  if constexpr (DMT_PSPK_GLDS) {
-    const int lsu = act ? ((a.term[blk] != 0 ? a.selPP[g] : a.selPPB[g]) ^ a.law_flip) : 0;
-    const int kdu = act && a.term[blk] == 0 ? 1 : 0;
-    glds_off = __ballot(act && (q0 != 0 || a.H_shared[lsu][kdu] != 0)) != 0;
-  }
-  if (glds_off || __ballot(act && ((row + 1) & (PK - 1)) != 0) != 0) {
-    if (w == 1 && act) lane_block_pk<Mdl, T, MODE_PCN, false, K, false, false, SDT>(a, tile, blk, lane, stg);
+  // both waves take the same branch (same lanes, same values)
+  if (__ballot(act && ((row + 1) & (PK - 1)) != 0) != 0) {
+    if (w == 1 && act) lane_block_pk<Mdl, T, MODE_PCN, false, K, false, false, SDT>(a, tile, blk, lane);
     return;
   }
   const int nst = act ? a.seg_np[g] - 1 : 0;
@@ -1472,22 +1287,7 @@ __global__ __launch_bounds__(128, 1) void k_block_ps_pk(const BlockArgs<T> a) {
         for (int bq = 0; bq < PK * M / NPB; ++bq) {
           const uint32_t bc = (uint32_t)((p * PK * M) / NPB + bq);
           T zb[NPB];
-#if DMT_PSPK_STUB & 2  // timing stub: the consumer alone (no normals drawn; wrong results)
-#pragma unroll
-          for (int e = 0; e < NPB; ++e) zb[e] = (T)(bc & 7) * (T)0.125;
-#else
           normal_block(philox4x32_10(U4{bc, ns.seg, ns.iter, ns.c3}, ns.k0, ns.k1), zb);
-#endif
-#if DMT_PSPK_STUB & 16  // timing probe (results unchanged): every normal block drawn twice
-          {
-            uint32_t bc2 = bc;
-            asm volatile("" : "+v"(bc2));
-            T zb2[NPB];
-            normal_block(philox4x32_10(U4{bc2, ns.seg, ns.iter, ns.c3}, ns.k0, ns.k1), zb2);
-#pragma unroll
-            for (int e = 0; e < NPB; ++e) asm volatile("" ::"v"(zb2[e]));
-          }
-#endif
 #pragma unroll
           for (int e = 0; e < NPB; ++e) z[(NPB * bq + e) / M][(NPB * bq + e) % M] = zb[e];
         }
@@ -1585,66 +1385,20 @@ __global__ __launch_bounds__(128, 1) void k_block_ps_pk(const BlockArgs<T> a) {
 #pragma unroll
       for (int j = 0; j < K; ++j) {
         const int64_t i = min<int64_t>(i0 + j, ilast);
-#if DMT_PSPK_STUB & 8  // timing stub: no H, F loads (wrong results)
-#pragma unroll
-        for (int e = 0; e < HP; ++e) s.H[j][e] = (T)(i & 3) * (T)0.01;
-#pragma unroll
-        for (int e = 0; e < D; ++e) s.F[j][e] = (T)(i & 7) * (T)0.01;
-#else
 #pragma unroll
         for (int e = 0; e < HP; ++e) s.H[j][e] = lane_ld(&Hb[(i * HP + e) * hst]);
 #pragma unroll
         for (int e = 0; e < D; ++e) s.F[j][e] = lane_ld(&Fb[(i * D + e) * kLanes]);
-#endif
       }
     };
-#if DMT_PSPK_GLDS
-    // LDS-DMA ring (every lane's segment at the tile's first row — the first segment of every
-    // recording, C5 — and per-point tables: a chunk of the tile's H, F rows is then one
-    // contiguous block, copied by 1 KB wave-instructions without registers, the loads of
-    // NGS - 1 chunks in flight).  The chunk's rows are read unclamped: a lane past its own
-    // segment end only evaluates steps it never adds or applies (the tile's spare rows keep
-    // every read inside the tile)
-    constexpr int NIH = GCH * (int)sizeof(T) / 1024, NIF = GCF * (int)sizeof(T) / 1024;
-    static_assert(GCH * sizeof(T) % 1024 == 0 && GCF * sizeof(T) % 1024 == 0, "whole 1 KB copies");
-    static_assert((NGS - 1) * K + K <= kPadPoints && (NGS - 1) * (NIH + NIF) <= 63, "ring depth");
-    const T* Ft = a.F[ls][kind];
-    auto gissue = [&](int64_t i0, int slot) {  // chunk of steps [i0, i0 + K) → slot
-      const T* hs = Ht + (tq + i0) * HP * kLanes + lane * (16 / (int)sizeof(T));
-      const T* fs = Ft + (tq + i0) * D * kLanes + lane * (16 / (int)sizeof(T));
-      const uint32_t l0 = (uint32_t)(uintptr_t)&hfr[slot][0];
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot's last reads retired (WAR)
-#pragma unroll
-      for (int j = 0; j < NIH; ++j)
-        glds16(hs + j * (1024 / (int)sizeof(T)), __builtin_amdgcn_readfirstlane(l0 + 1024u * j));
-#pragma unroll
-      for (int j = 0; j < NIF; ++j)
-        glds16(fs + j * (1024 / (int)sizeof(T)),
-               __builtin_amdgcn_readfirstlane(l0 + (uint32_t)(GCH * sizeof(T)) + 1024u * j));
-    };
-    auto gread = [&](int slot, Sub& s) {
-#pragma unroll
-      for (int j = 0; j < K; ++j) {
-#pragma unroll
-        for (int e = 0; e < HP; ++e) s.H[j][e] = hfr[slot][(j * HP + e) * 64 + lane];
-#pragma unroll
-        for (int e = 0; e < D; ++e) s.F[j][e] = hfr[slot][GCH + (j * D + e) * 64 + lane];
-      }
-    };
-#endif
     // H, F chunks in flight: a ring of NR register sets, NR - 1 chunks ahead; NR divides the
     // packet's chunks, so the unrolled packet loop indexes the ring with constants (the consumer
     // has little arithmetic per step to cover the loads' latency with)
     constexpr int NR = DMT_PSPK_RING;
     static_assert((PK / K) % NR == 0 && (NR - 1) * K <= kPadPoints, "ring of whole packets");
-#if DMT_PSPK_GLDS
-#pragma unroll
-    for (int u = 0; u < NGS - 1; ++u) gissue((int64_t)u * K, u);
-#else
     Sub sb[NR];
 #pragma unroll
     for (int u = 0; u < NR - 1; ++u) load((int64_t)u * K, sb[u]);
-#endif
     for (int c = -1; c < nch; ++c) {
       if (c >= 0) {
         const int buf = c & 1;
@@ -1652,18 +1406,8 @@ __global__ __launch_bounds__(128, 1) void k_block_ps_pk(const BlockArgs<T> a) {
 #pragma unroll
         for (int q = 0; q < PK / K; ++q) {
           const int64_t i0 = (int64_t)c * PK + q * K;
-#if DMT_PSPK_GLDS
-          // chunk jj + NGS - 1 into the slot chunk jj - 1 was read from; chunk jj's copies are
-          // the oldest loads outstanding but the (NGS - 1)(NIH + NIF) issued after them
-          const int jj = c * (PK / K) + q;
-          gissue(i0 + (NGS - 1) * K, (jj + NGS - 1) % NGS);
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NGS - 1) * (NIH + NIF)) : "memory");
-          Sub cur;
-          gread(jj % NGS, cur);
-#else
           load(i0 + (NR - 1) * K, sb[(q + NR - 1) % NR]);  // prefetch NR - 1 chunks ahead
           Sub& cur = sb[q % NR];
-#endif
           T gv[K];
 #pragma unroll
           for (int j = 0; j < K; ++j) {
@@ -1674,11 +1418,6 @@ __global__ __launch_bounds__(128, 1) void k_block_ps_pk(const BlockArgs<T> a) {
 #pragma unroll
             for (int k = 0; k < M; ++k) dW[k] = s_dw[buf][e][k][lane];
             T xn[D];
-#if DMT_PSPK_STUB & 1  // timing stub: the producer alone (no recursion; wrong results)
-            const T G = cur.H[j][0] + cur.F[j][0];
-#pragma unroll
-            for (int p = 0; p < D; ++p) xn[p] = x[p] + dW[p % M] * dt;
-#else
             T rr[D], b[D], sdW[D], Mg[D * D], cg[D];
             const T G = g_at<Mdl, T>(LA, cur.H[j], cur.F[j], x, rr, b);
             bool fast = false;
@@ -1697,24 +1436,6 @@ __global__ __launch_bounds__(128, 1) void k_block_ps_pk(const BlockArgs<T> a) {
 #pragma unroll
             for (int p = 0; p < D; ++p) xn[p] = x[p];
             euler_step<Mdl, T>(LA.th, Mg, cg, b, dt, sdW, xn);
-#if DMT_PSPK_STUB & 32  // timing probe (results unchanged): every step's arithmetic twice
-            {
-              T x2[D], r2[D], b2[D], M2[D * D], c2[D], H2[HP], F2[D];
-#pragma unroll
-              for (int p = 0; p < D; ++p) { x2[p] = x[p]; asm volatile("" : "+v"(x2[p])); }
-#pragma unroll
-              for (int e2 = 0; e2 < HP; ++e2) { H2[e2] = cur.H[j][e2]; asm volatile("" : "+v"(H2[e2])); }
-#pragma unroll
-              for (int e2 = 0; e2 < D; ++e2) { F2[e2] = cur.F[j][e2]; asm volatile("" : "+v"(F2[e2])); }
-              const T G2 = g_at<Mdl, T>(LA, H2, F2, x2, r2, b2);
-              guide_coeffs<Mdl, T>(LA, H2, F2, M2, c2);
-              euler_step<Mdl, T>(LA.th, M2, c2, b2, dt, sdW, x2);
-              asm volatile("" ::"v"(G2));
-#pragma unroll
-              for (int p = 0; p < D; ++p) asm volatile("" ::"v"(x2[p]));
-            }
-#endif
-#endif
 #pragma unroll
             for (int p = 0; p < D; ++p) {
               x[p] = v ? xn[p] : x[p];
@@ -1730,7 +1451,7 @@ __global__ __launch_bounds__(128, 1) void k_block_ps_pk(const BlockArgs<T> a) {
               if (i0 + j < nst) ps.add(gv[j]);
           }
         }
-        if (act && !(DMT_PSPK_STUB & 4)) {  // (timing stub 4: no X° stores)
+        if (act) {
           if ((int64_t)(c + 1) * PK <= nst) {  // a whole piece
             if (pair && (c & 1) == 0 && (int64_t)(c + 2) * PK <= nst) {  // first half: LDS
 #pragma unroll
@@ -1955,18 +1676,7 @@ struct ChunkIt {  // (segment, first step) iterator over a block's chunks of 64 
   }
 };
 
-#ifndef DMT_S_UNROLL
-#define DMT_S_UNROLL 4
-#endif
-#ifndef DMT_S_LDS_CAPTURE  // wave S captures x_s through an LDS store of lane 0 (1) or a
-#define DMT_S_LDS_CAPTURE 1  // register select in lane s (0)
-#endif
-#ifndef DMT_S_FULL_UNROLL  // whole 64-step chunks straight-line (1) or the DMT_S_UNROLL loop (0)
-#define DMT_S_FULL_UNROLL 1
-#endif
-#ifndef DMT_S_AHEAD  // rows read this many steps ahead in the straight-line chunk
-#define DMT_S_AHEAD 2
-#endif
+constexpr int kSUnroll = 4;  // unroll of wave S's loop over a segment's last, partial chunk
 // DIAG (timing diagnostics only, never selected in production): bit 0 = S skips its
 // recursion, bit 1 = P skips phase A, bit 2 = P skips phase B.
 template <class Mdl, class T, int MODE, int DIAG = 0>
@@ -2015,27 +1725,19 @@ __global__ __launch_bounds__(128) void k_block_wave(const BlockArgs<T> a) {
       const int cnt = (DIAG & 1) ? 0 : min(64, it.nst - it.c0);
       const T(*rw)[NR] = sh.rows[k & 1];
       T(*const xw)[D] = sh.xcap[k & 1];
-#if DMT_S_LDS_CAPTURE
       // lanes past the chunk's last step keep the chunk's start point (as the register capture)
       if (lane >= cnt) {
 #pragma unroll
         for (int p = 0; p < D; ++p) xw[lane][p] = x[p];
       }
-#else
-      T xc[D];
-#pragma unroll
-      for (int p = 0; p < D; ++p) xc[p] = x[p];
-#endif
       // the next step's row is read into registers one step ahead, so the LDS latency overlaps
       // the current step's dependent chain instead of preceding it
       T nx[NR];
 #pragma unroll
       for (int i = 0; i < NR; ++i) nx[i] = rw[0][i];
       // step s of the chunk from its row q.  x_s is captured for phase B: lane 0 writes it to
-      // the LDS row s (DMT_S_LDS_CAPTURE; an exec-masked store, no VALU), or lane s keeps it in
-      // a register (four v_cndmask and a compare per step, on the serial chain's wave)
+      // the LDS row s (an exec-masked store, no VALU)
       auto body = [&](const int s, const T* q) {
-#if DMT_S_LDS_CAPTURE
         if (lane == 0) {
           if constexpr (D == 2) {  // one 16/8-byte store at an immediate offset
             typedef T t2 __attribute__((ext_vector_type(2)));
@@ -2045,11 +1747,6 @@ __global__ __launch_bounds__(128) void k_block_wave(const BlockArgs<T> a) {
             for (int p = 0; p < D; ++p) xw[s][p] = x[p];
           }
         }
-#else
-        const bool mine = lane == s;
-#pragma unroll
-        for (int p = 0; p < D; ++p) xc[p] = mine ? x[p] : xc[p];
-#endif
         if constexpr (Mdl::kAffineStep) {
           Mdl::step_apply(q, x);  // the row is the step's map (Mdl::step_map, phase A)
         } else {
@@ -2058,7 +1755,6 @@ __global__ __launch_bounds__(128) void k_block_wave(const BlockArgs<T> a) {
           euler_step<Mdl, T>(L.th, q + 1 + D, q + 1 + D + D * D, b_, q[0], q + 1, x);
         }
       };
-#if DMT_S_FULL_UNROLL
       if (cnt == 64) {
         // a whole chunk (all but a segment's last): straight-line, no loop control, the rows
         // read DMT_S_AHEAD steps ahead into a register ring indexed by constants
@@ -2080,10 +1776,8 @@ __global__ __launch_bounds__(128) void k_block_wave(const BlockArgs<T> a) {
           for (int i = 0; i < NR; ++i) rb[s % AH][i] = rw[sn][i];
           body(s, q);
         }
-      } else
-#endif
-      {
-#pragma unroll DMT_S_UNROLL
+      } else {
+#pragma unroll kSUnroll
         for (int s = 0; s < cnt; ++s) {  // the row read one step ahead
           T q[NR];
 #pragma unroll
@@ -2094,10 +1788,6 @@ __global__ __launch_bounds__(128) void k_block_wave(const BlockArgs<T> a) {
           body(s, q);
         }
       }
-#if !DMT_S_LDS_CAPTURE
-#pragma unroll
-      for (int p = 0; p < D; ++p) xw[lane][p] = xc[p];
-#endif
       const bool seg_end = it.c0 + 64 >= it.nst;
       if (seg_end && lane == 0) {
 #pragma unroll
@@ -2352,52 +2042,10 @@ __device__ __forceinline__ float lane_read(float v, int addr) {
   return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, v)));
 }
 
-// DPP moves (VALU, no LDS round trip): lane l receives lane src(l) of the pattern CTRL in the
-// rows ROWMASK enables; the other lanes keep their own value (bound_ctrl off, old = v).
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ double dpp_mov(double v) {
-  const int2 p = __builtin_bit_cast(int2, v);
-  int2 r;
-  r.x = __builtin_amdgcn_update_dpp(p.x, p.x, CTRL, ROWMASK, 0xF, false);
-  r.y = __builtin_amdgcn_update_dpp(p.y, p.y, CTRL, ROWMASK, 0xF, false);
-  return __builtin_bit_cast(double, r);
-}
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ float dpp_mov(float v) {
-  const int p = __builtin_bit_cast(int, v);
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(p, p, CTRL, ROWMASK, 0xF, false));
-}
-constexpr int kDppRowShr = 0x110;    // row_shr:n = kDppRowShr + n (within rows of 16 lanes)
-constexpr int kDppRowBcast15 = 0x142;  // lane 15 of a row → the next row
-constexpr int kDppRowBcast31 = 0x143;  // lane 31 → rows 2 and 3
-[[maybe_unused]] constexpr int kDppWaveShr1 = 0x138;    // lane l − 1 → lane l
-
-// One level of the wave's inclusive scan of affine maps: lanes with `take` compose their map
-// after the map DPP pattern CTRL brings them (An = own ∘ received, affine_compose's order).
-template <int CTRL, int ROWMASK, int D, class T>
-__device__ __forceinline__ void affine_scan_level(T* RA, T* Re, const bool take) {
-  T Ap[D * D], ep[D], An[D * D], en[D];
-#pragma unroll
-  for (int c = 0; c < D * D; ++c) Ap[c] = dpp_mov<CTRL, ROWMASK>(RA[c]);
-#pragma unroll
-  for (int c = 0; c < D; ++c) ep[c] = dpp_mov<CTRL, ROWMASK>(Re[c]);
-  affine_compose<D, T>(RA, Re, Ap, ep, An, en);
-#pragma unroll
-  for (int c = 0; c < D * D; ++c) RA[c] = take ? An[c] : RA[c];
-#pragma unroll
-  for (int c = 0; c < D; ++c) Re[c] = take ? en[c] : Re[c];
-}
-// Inclusive scan of the 64 lanes' maps (lane j ← map_j ∘ … ∘ map_0).  DMT_SCAN_DPP = 1: the DPP
-// tree the oracle restates with ORC_SCAN_DPP = 1 (dmt_oracle.c wave_scan_dpp) — Kogge–Stone
-// within each row of 16 lanes (shifts 1, 2, 4, 8), then rows 1 and 3 compose after lane 15 /
-// lane 47 (row_bcast:15), then rows 2 and 3 after lane 31 (row_bcast:31); every level is VALU
-// work, no ds_bpermute round trip on the chain.  0: the 64-lane Kogge–Stone over ds_bpermute.
-#ifndef DMT_SCAN_DPP  // 0: the 64-lane Kogge–Stone over ds_bpermute (oracle ORC_SCAN_DPP = 0)
-#define DMT_SCAN_DPP 0
-#endif
+// Inclusive scan of the 64 lanes' maps (lane j ← map_j ∘ … ∘ map_0): the 64-lane Kogge–Stone
+// over ds_bpermute (the oracle's wave_scan).
 template <int D, class T>
 __device__ __forceinline__ void wave_affine_scan(T* RA, T* Re, const int lane) {
-#if !DMT_SCAN_DPP
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
     T Ap[D * D], ep[D], An[D * D], en[D];
@@ -2413,28 +2061,15 @@ __device__ __forceinline__ void wave_affine_scan(T* RA, T* Re, const int lane) {
 #pragma unroll
     for (int c = 0; c < D; ++c) Re[c] = take ? en[c] : Re[c];
   }
-  return;
-#endif
-  const int rl = lane & 15;
-  affine_scan_level<kDppRowShr + 1, 0xF, D, T>(RA, Re, rl >= 1);
-  affine_scan_level<kDppRowShr + 2, 0xF, D, T>(RA, Re, rl >= 2);
-  affine_scan_level<kDppRowShr + 4, 0xF, D, T>(RA, Re, rl >= 4);
-  affine_scan_level<kDppRowShr + 8, 0xF, D, T>(RA, Re, rl >= 8);
-  affine_scan_level<kDppRowBcast15, 0xA, D, T>(RA, Re, (lane & 16) != 0);
-  affine_scan_level<kDppRowBcast31, 0xC, D, T>(RA, Re, lane >= 32);
 }
 // The exclusive form's start points: lane l receives lane l − 1's value (lane 0: its own)
 template <class T>
 __device__ __forceinline__ T wave_shr1(T v) {
-#if DMT_SCAN_DPP
-  return dpp_mov<kDppWaveShr1, 0xF>(v);
-#else
   return lane_read(v, 4 * ((int)(threadIdx.x & 63) - 1));
-#endif
 }
 
 // store_row with nontemporal stores (the path stores of the resident MCMC kernels: written
-// once per iteration, read by no later iteration of the launch, DMT_PC_NT_STORES)
+// once per iteration, read by no later iteration of the launch)
 template <int N, class T>
 __device__ __forceinline__ void store_row_nt(T* p, const T* v) {
   if constexpr (std::is_same<T, double>::value && N % 2 == 0) {
@@ -2449,11 +2084,6 @@ __device__ __forceinline__ void store_row_nt(T* p, const T* v) {
 // Store one point's N components (16-byte stores when N is even and T is double).
 template <int N, class T>
 __device__ __forceinline__ void store_row(T* p, const T* v) {
-#if defined(DMT_PATH_STORE_WT)  // experiment: write-through path stores
-#pragma unroll
-  for (int c = 0; c < N; ++c) __hip_atomic_store(p + c, v[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return;
-#endif
   if constexpr (std::is_same<T, double>::value && N % 2 == 0) {
 #pragma unroll
     for (int c = 0; c < N; c += 2) *reinterpret_cast<double2*>(p + c) = make_double2(v[c], v[c + 1]);
@@ -2461,18 +2091,6 @@ __device__ __forceinline__ void store_row(T* p, const T* v) {
 #pragma unroll
     for (int c = 0; c < N; ++c) p[c] = v[c];
   }
-}
-
-#ifndef DMT_PC_NT_STORES
-#define DMT_PC_NT_STORES 1
-#endif
-template <int N, class T>
-__device__ __forceinline__ void store_row_pc(T* p, const T* v) {
-#if DMT_PC_NT_STORES
-  store_row_nt<N, T>(p, v);
-#else
-  store_row<N, T>(p, v);
-#endif
 }
 
 // Path selectors of the scan kernels: read from the ensemble arrays (one launch per call;
@@ -2878,35 +2496,19 @@ __device__ __forceinline__ void st_sc1(double* p, double v) {
 // "Hand-offs measured with sc1 loads", row 1: sc1 stores drained by every storing wave, one
 // lane per workgroup adds to one unsharded counter after a barrier, the last adder — told by
 // its add's return — loads with sc1; hipMalloc memory, one workgroup per CU), not an API
-// guarantee.  DMT_TREE_FENCES=1 (measurement build) adds the API's agent-scope release before
-// the add and acquire after it (their price per C2 launch).
-#ifndef DMT_TREE_FENCES
-#define DMT_TREE_FENCES 0
-#endif
+// guarantee (the price per C2 launch of the API's agent-scope release before the
+// add and acquire after it).
 __device__ __forceinline__ bool arrive_last(unsigned* cnt, unsigned expect, int* s_flag) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) {
-#if DMT_TREE_FENCES
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     *s_flag = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
                       expect - 1 ? 1 : 0;
-#if DMT_TREE_FENCES
-    if (*s_flag) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-#endif
   }
   __syncthreads();
   return *s_flag != 0;
 }
 
-#ifndef DMT_TREE_ONEHOP  // persistent_tree_tail: one arrival hop for <= 256 workgroups (1) —
-#define DMT_TREE_ONEHOP 0  // measured 2 µs slower per C2 launch than the two hops (profiles/r03end)
-#endif
 // nodes: node1 [rows][ng] then node2 [rows][ng2]; counters: [ng2] group counters then the top
 // counter, zero on entry and left zero.  WPB = blocks (tree leaves) per workgroup, NW = waves
 // per workgroup (every thread of the workgroup calls this)
@@ -2939,35 +2541,6 @@ __device__ __forceinline__ void persistent_tree_tail(const double* __restrict__ 
       for (int k = 0; k < w / 2; ++k) v[k] = v[2 * k] + v[2 * k + 1];
     st_sc1(&node1[row * ng + x], v[0]);
   }
-#if DMT_TREE_ONEHOP
-  if (ng <= 256 && rows * ng <= 32768) {
-    // few workgroups and rows (C2 at the driver's 20 iterations: 256 x 60): one arrival over all of them, then each row's tree over its ng
-    // level-1 nodes as 64 lanes x 4 adjacent leaves (zero-padded to 256) — the same complete
-    // adjacent-pair tree as the two-hop form below, whose 16 x 16 grouping it skips
-    if (!arrive_last(&counters[ng2], (unsigned)ng, &s_flag)) return;
-    constexpr int RB = 8;  // rows per wave per batch (4 RB loads per lane in flight)
-    for (int64_t r0 = (int64_t)wv * RB; r0 < rows; r0 += (int64_t)NW * RB) {
-      double v[RB][4];
-#pragma unroll
-      for (int b = 0; b < RB; ++b)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int64_t row = r0 + b, nd = 4 * lane + k;
-          v[b][k] = (row < rows && nd < ng) ? ld_sc1(&node1[row * ng + nd]) : 0.0;
-        }
-#pragma unroll
-      for (int b = 0; b < RB; ++b) {
-        const double t = wave_tree_sum<double>((v[b][0] + v[b][1]) + (v[b][2] + v[b][3]));
-        const int64_t row = r0 + b;
-        if (lane == 0 && row < rows) out3[row] = (row % 3 == 2) ? t : t + 0.0;
-      }
-    }
-    __syncthreads();
-    if (tid == 0)  // ready for the next launch (stream-ordered)
-      __hip_atomic_store(&counters[ng2], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return;
-  }
-#endif
   const int64_t gsize = ng - g * kTreeGroup < kTreeGroup ? ng - g * kTreeGroup : kTreeGroup;
   if (!arrive_last(&counters[g], (unsigned)gsize, &s_flag)) return;
   // ---- level 2: group g's nodes, 16 lanes per row, NT/16 rows per pass, U passes in flight
@@ -3429,13 +3002,8 @@ __global__ __launch_bounds__(256, 1) void k_mcmc_resident(const BlockArgs<T> a,
   __shared__ ResLds<Mdl::D, Mdl::M, T> lds[4];
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t blk = a.b0 + (int64_t)blockIdx.x * 4 + w;
-#ifdef DMT_VARIANT_EARLY_RETURN  // measurement variant: no in-kernel trees (out3 not written)
-  if (blk >= a.b1) return;
-  resident_block<Mdl, T, MODE_PCN, true>(a, c, iter0, n_iter, part, blk, lds[w]);
-#else
   if (blk < a.b1) resident_block<Mdl, T, MODE_PCN, true>(a, c, iter0, n_iter, part, blk, lds[w]);
   persistent_tree_tail<4>(part, nodes, a.b1 - a.b0, n_iter, counter, out3);
-#endif
 }
 
 // ---- k_mcmc_resident split over two waves per block (producer / consumer).
@@ -3454,29 +3022,34 @@ __global__ __launch_bounds__(256, 1) void k_mcmc_resident(const BlockArgs<T> a,
 // order are resident_block's: bit-identical results (the GPU tests run both).
 // Measurement build only (-DDMT_PC_STAMPS, scripts/pc_stamps.py): device wall-clock stamps of
 // one k_mcmc_resident_pc launch per workgroup — entry, the consumer's and the producer's set-up
-// done, B1 of iteration 0 passed, the loop's end, the tail's end (dmt_probe_pc_stamps).
+// done, B1 of iteration 0 passed, the loop's end, the tail's end (dmt_probe_pc_stamps).  Each
+// (precision, model) unit stamps its own arrays; the readers are the fp64 OU unit's (C2).
 #ifdef DMT_PC_STAMPS
-__device__ uint64_t g_pc_stamps[8192 * 8];
+[[maybe_unused]] static __device__ uint64_t g_pc_stamps[8192 * 8];
 #define PC_STAMP(TID, K)                                                                  \
   do {                                                                                    \
     if (threadIdx.x == (TID) && blockIdx.x < 8192)                                        \
       g_pc_stamps[blockIdx.x * 8 + (K)] = (uint64_t)wall_clock64();                        \
   } while (0)
+#if DMT_TU_GROUP == 0
 extern "C" int dmt_probe_pc_stamps(uint64_t* out, int64_t n) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pc_stamps), (size_t)std::min<int64_t>(n, 8192 * 8) * 8);
 }
+#endif
 // per iteration r < 64 of workgroup 0: consumer after B1 (0), its decision made (1), at B2 (2),
 // after B2 (3); producer after B1 (4), at B2 with the next normals drawn (5), after B2 (6), at
 // B1 with the next proposal handed over (7)
-__device__ uint64_t g_pc_it[64 * 8];
+[[maybe_unused]] static __device__ uint64_t g_pc_it[64 * 8];
 #define PC_ITSTAMP(TID, R, K)                                                             \
   do {                                                                                    \
     if (threadIdx.x == (TID) && blockIdx.x == 0 && (R) < 64)                              \
       g_pc_it[(R) * 8 + (K)] = (uint64_t)wall_clock64();                                   \
   } while (0)
+#if DMT_TU_GROUP == 0
 extern "C" int dmt_probe_pc_iter_stamps(uint64_t* out) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pc_it), 64 * 8 * 8);
 }
+#endif
 #else
 #define PC_STAMP(TID, K) \
   do {                   \
@@ -3484,21 +3057,6 @@ extern "C" int dmt_probe_pc_iter_stamps(uint64_t* out) {
 #define PC_ITSTAMP(TID, R, K) \
   do {                        \
   } while (0)
-#endif
-#ifndef DMT_PC_DRAW_GROUP
-#define DMT_PC_DRAW_GROUP 8
-#endif
-#ifndef DMT_PC_LATE_C  // the consumer forms its own steps' next proposal after B2
-#define DMT_PC_LATE_C 1
-#endif
-#ifndef DMT_PC_SPEC  // the producer forms both candidates of the next proposal before B2
-#define DMT_PC_SPEC 1
-#endif
-#ifndef DMT_PC_SETUP_OVERLAP  // set-up loads in flight while the first normals are drawn
-#define DMT_PC_SETUP_OVERLAP 1
-#endif
-#ifndef DMT_PC_CONS_STEPS
-#define DMT_PC_CONS_STEPS 2
 #endif
 // With one producer, the consumer draws the normals (and forms dW°, e) of the last CR steps of
 // every lane run itself, filling its own latency bubbles and shortening the producer's chain;
@@ -3519,9 +3077,6 @@ struct SvcLds {
   int go;             // the gate's answer
   double row[3][4];   // the iteration's (ll, ll°, accepted) of the workgroup's 4 blocks
 };
-#ifndef DMT_SVC_PEEK  // the gate's host words read ahead (svc_peek): 1 after the iteration's
-#define DMT_SVC_PEEK 1   // points, 2 after its scan; 0: at the gate only
-#endif
 // Gate of iteration r (in place of its B1 barrier).  Workgroup 0's thread 0 is the launch's one
 // reader of host memory: it waits until the host has posted iteration r, asked the launch to
 // stop, or stayed silent for idle_ticks, and publishes the answer in device memory — go word
@@ -3540,12 +3095,10 @@ struct SvcPeek {
 };
 __device__ __forceinline__ SvcPeek svc_peek(const SvcArgs& sv) {
   SvcPeek p;
-#if DMT_SVC_PEEK
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     p.stop = __hip_atomic_load(sv.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     p.posted = __hip_atomic_load(sv.posted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
-#endif
   return p;
 }
 __device__ __forceinline__ bool svc_gate(const SvcArgs& sv, int64_t r, SvcLds* sl,
@@ -3618,15 +3171,10 @@ __device__ __forceinline__ void svc_record(const SvcArgs& sv, const SvcLds* sl, 
 #endif
 }
 
-#ifndef DMT_PC_L1_LOOP  // 1: level 1 of the fetch_ll trees formed during the run (after B2);
-                        // 0: read back from part[] by persistent_tree_tail
-#define DMT_PC_L1_LOOP 1
-#endif
 template <class Mdl, class T, int NP, bool SVC, int BPW = 4>
 __device__ __forceinline__ void resident_pc_consumer(const BlockArgs<T>& a, const AcceptArgs& c,
                                                      const int64_t iter0, const int64_t n_iter,
-                                                     double* __restrict__ part, const int64_t blk,
-                                                     const bool valid,
+                                                     const int64_t blk, const bool valid,
                                                      ResPcLds<Mdl::D, Mdl::M, T>& P,
                                                      const SvcArgs& sv, SvcLds* sl,
                                                      double* __restrict__ nodes = nullptr) {
@@ -3669,11 +3217,9 @@ __device__ __forceinline__ void resident_pc_consumer(const BlockArgs<T>& a, cons
         for (int k = 0; k < M; ++k) zC[r][k] = zz[r * M + k];
     }
   };
-#if DMT_PC_SETUP_OVERLAP
   // the first iteration's normals of the consumer's steps: they need the block's segment
   // only, so their arithmetic runs while the metadata and per-step loads below are in flight
   draw_c((uint32_t)(iter0 + c.key_delta));
-#endif
   const int64_t row = tq + q0;
   const int kind = term ? 0 : 1;
   const int ls = (kind ? ldc(a.selPPB + g) : ldc(a.selPP + g)) ^ a.law_flip;
@@ -3769,14 +3315,10 @@ __device__ __forceinline__ void resident_pc_consumer(const BlockArgs<T>& a, cons
     }
   };
   PC_STAMP(0, 7);
-#if !DMT_PC_SETUP_OVERLAP
-  draw_c((uint32_t)(iter0 + c.key_delta));
-#endif
   propose_c();
   hand_dw();
   const uint64_t all = 1;
   double ll = valid ? c.ll[blk] : 0.0, llp = 0.0;
-  const int64_t nb = a.b1 - a.b0, j = blk - a.b0;
   const int last_lane = (nst - 1) / kRun;
   double Ev = 0.0;
   PC_STAMP(0, 1);
@@ -3822,7 +3364,6 @@ __device__ __forceinline__ void resident_pc_consumer(const BlockArgs<T>& a, cons
     }
     wave_affine_scan<D, T>(RA, Re, lane);
     SvcPeek peek;  // (the service: the gate's host words, requested ahead — svc_peek)
-    if constexpr (SVC && DMT_SVC_PEEK == 2) peek = svc_peek(sv);
     T x[D];
     {
       T y[D];
@@ -3855,7 +3396,7 @@ __device__ __forceinline__ void resident_pc_consumer(const BlockArgs<T>& a, cons
       for (int p = 0; p < D; ++p) x[p] = v ? xn[p] : x[p];
     }
     // (the service: the gate's host words requested now, answered while the trees finish)
-    if constexpr (SVC && DMT_SVC_PEEK == 1) peek = svc_peek(sv);
+    if constexpr (SVC) peek = svc_peek(sv);
     T xe[D];
 #pragma unroll
     for (int p = 0; p < D; ++p) xe[p] = lane_value(x[p], last_lane);  // uniform: v_readlane
@@ -3893,10 +3434,10 @@ __device__ __forceinline__ void resident_pc_consumer(const BlockArgs<T>& a, cons
           T xv[D];
 #pragma unroll
           for (int p = 0; p < D; ++p) xv[p] = S.pt[lds_ix(s)][p];
-          store_row_pc<D, T>(Xdb + (int64_t)s * D, xv);
+          store_row_nt<D, T>(Xdb + (int64_t)s * D, xv);
         }
       }
-      if (lane == 0) store_row_pc<D, T>(Xdb + (int64_t)nst * D, xe);
+      if (lane == 0) store_row_nt<D, T>(Xdb + (int64_t)nst * D, xe);
     }
     bool sok = isfinite(seg_acc);
 #pragma unroll
@@ -3918,13 +3459,8 @@ __device__ __forceinline__ void resident_pc_consumer(const BlockArgs<T>& a, cons
           c.ll_hist[o] = ll;
           c.llp_hist[o] = llp;
         }
-        if constexpr (!SVC && !DMT_PC_L1_LOOP) {
-          part[(3 * r0 + 0) * nb + j] = acc ? llp : ll;
-          part[(3 * r0 + 1) * nb + j] = acc ? ll : llp;
-          part[(3 * r0 + 2) * nb + j] = acc ? 1.0 : 0.0;
-        }
       }
-      if constexpr (!SVC && DMT_PC_L1_LOOP) {  // the workgroup's fetch_ll leaves (0: no block)
+      if constexpr (!SVC) {  // the workgroup's fetch_ll leaves (0: no block)
         const int wi = (int)(threadIdx.x >> 6) % BPW;
         sl->row[0][wi] = valid ? (acc ? llp : ll) : 0.0;
         sl->row[1][wi] = valid ? (acc ? ll : llp) : 0.0;
@@ -3943,15 +3479,11 @@ __device__ __forceinline__ void resident_pc_consumer(const BlockArgs<T>& a, cons
 #pragma unroll
           for (int k = 0; k < M; ++k) wvC[r][k] = dWC[r][k];
       }
-      if constexpr (!SVC && !DMT_PC_LATE_C) {
-        wave_lds_sync();  // this wave's pt reads of the X° stores above are done
-        propose_c();
-      }
     }
     PC_ITSTAMP(0, r0, 2);
     __syncthreads();  // B2: decision n → producer; pt reads of this iteration done
     PC_ITSTAMP(0, r0, 3);
-    if constexpr (!SVC && DMT_PC_L1_LOOP) {
+    if constexpr (!SVC) {
       // level 1 of iteration n's fetch_ll trees (persistent_tree_tail): the workgroup's BPW
       // leaves, adjacent pairs, stored write-through now instead of read back after the run
       if (threadIdx.x < 3) {
@@ -3966,9 +3498,9 @@ __device__ __forceinline__ void resident_pc_consumer(const BlockArgs<T>& a, cons
         st_sc1(&nodes[(3 * r0 + threadIdx.x) * ng + blockIdx.x], v[0]);
       }
     }
-    // (DMT_PC_LATE_C: the consumer's own steps of iteration n + 1 after B2, beside the producer's
+    // (the consumer's own steps of iteration n + 1 after B2, beside the producer's
     // proposal — the consumer, not the producer, is the one late at B2)
-    if constexpr (!SVC && DMT_PC_LATE_C && CR > 0) propose_c();
+    if constexpr (!SVC && CR > 0) propose_c();
     if constexpr (SVC) {
       if constexpr (CR > 0) {
         draw_c((uint32_t)(it + 1 + c.key_delta));
@@ -4036,19 +3568,8 @@ __device__ __forceinline__ void resident_pc_producer(const BlockArgs<T>& a, cons
     asm volatile("" : "+v"(ln));
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
-#if defined(DMT_PROBE_NO_BM)  // timing probes only (wrong normals): Philox without Box–Muller
-      {
-        const U4 o = philox4x32_10(U4{ln + q, (uint32_t)g + a.seg_base, itv, c3}, k0, k1);
-        zz[NPB * q] = (T)(o.x ^ o.y) * (T)0x1p-32;
-        zz[NPB * q + 1] = (T)(o.z ^ o.w) * (T)0x1p-32;
-      }
-#elif defined(DMT_PROBE_NO_PHILOX)  // Box–Muller without Philox
-      normal_block(U4{(ln + q) ^ itv, (ln + q) * 0x9E3779B9u ^ itv, itv * 3u + q, c3 ^ ln},
-                   zz + NPB * q);
-#else
       normal_block(philox4x32_10(U4{ln + q, (uint32_t)g + a.seg_base, itv, c3}, k0, k1),
                    zz + NPB * q);
-#endif
       // DMT_PC_DRAW_GROUP Philox blocks + Box–Muller interleaved at a time
       if ((q + 1) % DMT_PC_DRAW_GROUP == 0) __builtin_amdgcn_sched_barrier(0);
     }
@@ -4058,11 +3579,9 @@ __device__ __forceinline__ void resident_pc_producer(const BlockArgs<T>& a, cons
       for (int kk = 0; kk < M; ++kk) z[r][kk] = zz[r * M + kk];
   };
   T z[RR][M], w0n[M];
-#if DMT_PC_SETUP_OVERLAP
   // the first iteration's normals: they need the block's segment only, so their arithmetic
   // runs while the metadata and per-step loads below are in flight (bit-identical)
   draw_z((uint32_t)(iter0 + c.key_delta), z);
-#endif
   const int64_t row = tq + q0;
   const bool term = ldc(&bi->term) != 0;
   const int kind = term ? 0 : 1;
@@ -4141,14 +3660,11 @@ __device__ __forceinline__ void resident_pc_producer(const BlockArgs<T>& a, cons
         T wd[M];
 #pragma unroll
         for (int kk = 0; kk < M; ++kk) wd[kk] = S.dw[lds_ix(s)][kk];
-        store_row_pc<M, T>(Wdb + (int64_t)(s + 1) * M, wd);
+        store_row_nt<M, T>(Wdb + (int64_t)(s + 1) * M, wd);
       }
     }
-    if (h == 0 && lane == 0) store_row_pc<M, T>(Wdb, w0n);
+    if (h == 0 && lane == 0) store_row_nt<M, T>(Wdb, w0n);
   };
-#if !DMT_PC_SETUP_OVERLAP
-  draw_z((uint32_t)(iter0 + c.key_delta), z);
-#endif
   propose();
   PC_STAMP(256, 2);  // producer 0 of workgroup block 0 (BPW = 4)
   __syncthreads();  // B1 of iteration 0
@@ -4159,11 +3675,10 @@ __device__ __forceinline__ void resident_pc_producer(const BlockArgs<T>& a, cons
     // the next iteration's normals (they depend on the stream key alone), while the consumer
     // runs this one, and both candidates of its pCN increments — u's increments are the
     // current proposal's if the consumer accepts it, else they stay — so that after B2 only a
-    // selection, σ·dW° and the e maps stand between the decision and B1 (DMT_PC_SPEC)
+    // selection, σ·dW° and the e maps stand between the decision and B1
     T dWa[RR][M], dWr[RR][M];
     if (more) {
       draw_z((uint32_t)(iter0 + r0 + 1 + c.key_delta), z);
-#if DMT_PC_SPEC
 #pragma unroll
       for (int r = 0; r < RR; ++r)
 #pragma unroll
@@ -4172,7 +3687,6 @@ __device__ __forceinline__ void resident_pc_producer(const BlockArgs<T>& a, cons
           dWa[r][kk] = dfma(rho, dWp[r][kk], q);
           dWr[r][kk] = dfma(rho, wv[r][kk], q);
         }
-#endif
     }
     if constexpr (SVC) {  // the service: W° of iteration n once the host has posted it
       if (!svc_gate(sv, r0, sl)) break;
@@ -4193,16 +3707,12 @@ __device__ __forceinline__ void resident_pc_producer(const BlockArgs<T>& a, cons
 #pragma unroll
       for (int k = 0; k < M; ++k) wv[r][k] = acc ? dWp[r][k] : wv[r][k];
     if (more) {
-#if DMT_PC_SPEC
       T dWn[RR][M];
 #pragma unroll
       for (int r = 0; r < RR; ++r)
 #pragma unroll
         for (int k = 0; k < M; ++k) dWn[r][k] = acc ? dWa[r][k] : dWr[r][k];
       propose_from(dWn);
-#else
-      propose();
-#endif
       PC_ITSTAMP(256, r0, 7);
       __syncthreads();  // B1: dW° of iteration n + 1 ready
       if constexpr (!SVC) store_w();
@@ -4230,27 +3740,15 @@ __global__ __launch_bounds__(64 * BPW * (NP + 1), BPW == 4 ? 1 : 2) void k_mcmc_
   const int64_t blk = a.b0 + (int64_t)blockIdx.x * BPW + (w % BPW);
   const bool valid = blk < a.b1;
   const int role = w / BPW;  // 0: consumer, 1 + h: producer h
-#if defined(DMT_PC_STUB_P)  // timing probes (scripts/res_usage.sh, gpu_variants.sh): one role only
   if (role == 0)
-    resident_pc_consumer<Mdl, T, NP, SVC>(a, c, iter0, n_iter, part, blk, valid, lds[w & 3], sv, &s_svc);
-  else for (int64_t i = 0; i < 2 * n_iter; ++i) __syncthreads();
-#elif defined(DMT_PC_STUB_C)
-  if (role > 0)
-    resident_pc_producer<Mdl, T, NP, SVC>(a, c, iter0, n_iter, blk, valid, role - 1, lds[w & 3], sv, &s_svc);
-  else for (int64_t i = 0; i < 2 * n_iter; ++i) __syncthreads();
-#else
-  if (role == 0)
-    resident_pc_consumer<Mdl, T, NP, SVC, BPW>(a, c, iter0, n_iter, part, blk, valid, lds[w % BPW],
-                                               sv, &s_svc, nodes);
+    resident_pc_consumer<Mdl, T, NP, SVC, BPW>(a, c, iter0, n_iter, blk, valid, lds[w % BPW], sv,
+                                               &s_svc, nodes);
   else
     resident_pc_producer<Mdl, T, NP, SVC>(a, c, iter0, n_iter, blk, valid, role - 1, lds[w % BPW],
                                           sv, &s_svc);
-#endif
-#ifndef DMT_PC_NO_TAIL  // timing probe: no in-kernel fetch_ll trees
   if constexpr (!SVC)  // the service forms each iteration's tree as the iteration ends
-    persistent_tree_tail<BPW, BPW * (NP + 1), DMT_PC_L1_LOOP != 0>(part, nodes, a.b1 - a.b0,
-                                                                    n_iter, counter, out3);
-#endif
+    persistent_tree_tail<BPW, BPW * (NP + 1), true>(part, nodes, a.b1 - a.b0, n_iter, counter,
+                                                    out3);
   PC_STAMP(0, 5);
 }
 
@@ -5297,9 +4795,7 @@ __global__ void k_flip(const FlipArgs f, const int32_t* gfirst, const int32_t* g
       if (f.sel[i] && !(f.only_nonterm[i] && tm))
         f.sel[i][g] = i < 2 ? sel_swap(f.sel[i][g]) : (uint8_t)(f.sel[i][g] ^ 1);  // paths: swap u/u°
 }
-#endif  // DMT_TU_COMMON
 
-#if DMT_TU_COMMON
 __global__ void k_swap_ll(double* ll, double* llp, int64_t b0, int64_t b1) {
   const int64_t blk = b0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (blk >= b1) return;
@@ -5307,9 +4803,7 @@ __global__ void k_swap_ll(double* ll, double* llp, int64_t b0, int64_t b1) {
   ll[blk] = llp[blk];
   llp[blk] = v;
 }
-#endif  // DMT_TU_COMMON
 
-#if DMT_TU_COMMON
 __global__ void k_save_ll(const double* ll, const double* llp, double* llh, double* llph,
                           int64_t nblocks, int64_t it0, int64_t b0, int64_t b1) {
   const int64_t blk = b0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -5460,9 +4954,7 @@ __global__ void k_tree_final(const double* __restrict__ in, int64_t nout, double
   out3[1] = in[nout] + 0.0;
   out3[2] = in[2 * nout];
 }
-#endif  // DMT_TU_COMMON
 
-#if DMT_TU_COMMON
 __global__ void k_debug_philox(uint64_t seed, const uint32_t* ctr, int64_t n, uint32_t* out,
                                double* normals) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -5504,16 +4996,8 @@ static void dlaunch(void (*k)(KArgs...), dim3 grid, dim3 block, hipStream_t s, A
   }
 }
 
-#ifndef DMT_KCHUNK
-#define DMT_KCHUNK 4
-#endif
-constexpr int kChunk = DMT_KCHUNK;  // lane-kernel steps per prefetch chunk
-static_assert(2 * kChunk <= kPadPoints, "prefetch reads up to 2 chunks past a segment end");
-#ifndef DMT_PK_KCHUNK  // the packet kernels' chunk (their guiding-term prefetch distance)
-#define DMT_PK_KCHUNK DMT_KCHUNK
-#endif
-constexpr int kPkChunk = DMT_PK_KCHUNK;
-static_assert(2 * kPkChunk <= kPadPoints, "prefetch reads up to 2 chunks past a segment end");
+constexpr int kChunk = DMT_KCHUNK;      // lane-kernel steps per prefetch chunk (dmt_tuning.h)
+constexpr int kPkChunk = DMT_PK_KCHUNK;  // the packet kernels' chunk (their guiding-term prefetch distance)
 
 template <class Mdl, class T>
 static hipError_t launch_block_t(int mapping, int mode, const void* args, int64_t nwaves,
@@ -5575,7 +5059,7 @@ static hipError_t launch_block_t(int mapping, int mode, const void* args, int64_
           return hipGetLastError();
         }
         if (mode == MODE_PCN && !par && !td && a.lane_split) {  // producer/consumer waves
-          if (DMT_PK_SDT_TABLE && a.t_shared && a.sdt)
+          if (a.t_shared && a.sdt)
             dlaunch(k_block_ps_pk<Mdl, T, kPkChunk, true>, grid, dim3(128), s, a);
           else
             dlaunch(k_block_ps_pk<Mdl, T, kPkChunk, false>, grid, dim3(128), s, a);
@@ -5588,7 +5072,7 @@ static hipError_t launch_block_t(int mapping, int mode, const void* args, int64_
               else dlaunch(k_block_pk<Mdl, T, MODE_PCN, false, kPkChunk, true>, grid, block, s, a);
             } else {
               if (par) dlaunch(k_block_pk<Mdl, T, MODE_PCN, true, kPkChunk>, grid, block, s, a);
-              else if (DMT_PK_SDT_TABLE && a.t_shared && a.sdt)  // shared grid: √dt table
+              else if (a.t_shared && a.sdt)  // shared grid: √dt table
                 dlaunch(k_block_pk<Mdl, T, MODE_PCN, false, kPkChunk, false, true>, grid, block, s, a);
               else dlaunch(k_block_pk<Mdl, T, MODE_PCN, false, kPkChunk>, grid, block, s, a);
             }
@@ -5603,7 +5087,7 @@ static hipError_t launch_block_t(int mapping, int mode, const void* args, int64_
               else dlaunch(k_block_pk<Mdl, T, MODE_FRESH, false, kPkChunk, true>, grid, block, s, a);
             } else {
               if (par) dlaunch(k_block_pk<Mdl, T, MODE_FRESH, true, kPkChunk>, grid, block, s, a);
-              else if (DMT_PK_SDT_TABLE && a.t_shared && a.sdt)
+              else if (a.t_shared && a.sdt)
                 dlaunch(k_block_pk<Mdl, T, MODE_FRESH, false, kPkChunk, false, true>, grid, block, s, a);
               else dlaunch(k_block_pk<Mdl, T, MODE_FRESH, false, kPkChunk>, grid, block, s, a);
             }
@@ -5788,20 +5272,15 @@ static hipError_t launch_pathll_t(int mapping, const void* args, int64_t nwaves,
   return hipGetLastError();
 }
 
-// Model dispatch.  One monolithic translation unit by default; the Makefile's split build
-// compiles this file seven times in parallel (DMT_TU_GROUP = 0..5: one (precision, model)
-// group's kernels and entry points, named <entry>_g<group>; DMT_TU_GROUP = -1 with
-// DMT_SPLIT: the model-independent kernels and launchers plus the dispatchers below), so a
+// Model dispatch.  The Makefile compiles this file seven times in parallel (DMT_TU_GROUP =
+// 0..5: one (precision, model) group's kernels and entry points, named <entry>_g<group>;
+// DMT_TU_GROUP = -1: the model-independent kernels and launchers plus the dispatchers below), so a
 // change to one model's kernels rebuilds in a fraction of the time.  Groups: 3·(precision) +
 // model — 0 f64 OU, 1 f64 FHN, 2 f64 Lorenz, 3 f32 OU, 4 f32 FHN, 5 f32 Lorenz.
 #define DMT_CAT_(a, b) a##b
 #define DMT_CAT(a, b) DMT_CAT_(a, b)
-#if DMT_TU_GROUP >= 0
 #define DMT_ENTRY(name) DMT_CAT(name, DMT_CAT(_g, DMT_TU_GROUP))
-#else
-#define DMT_ENTRY(name) name
-#endif
-#define DMT_GROUP_ON(g) (!DMT_SPLIT || DMT_TU_GROUP == (g))
+#define DMT_GROUP_ON(g) (DMT_TU_GROUP == (g))
 #if DMT_GROUP_ON(0)
 #define DMT_CASE_0(KEY, CALL)                                                          \
   if ((KEY).precision == DMT_F64 && (KEY).model == DMT_MODEL_OU) {                     \
@@ -5869,7 +5348,7 @@ static hipError_t launch_pathll_t(int mapping, const void* args, int64_t nwaves,
     return hipErrorInvalidValue;                                                       \
   } while (0)
 
-#if !DMT_SPLIT || DMT_TU_GROUP >= 0
+#if DMT_TU_GROUP >= 0
 hipError_t DMT_ENTRY(launch_block_kernel)(const ModelKey& k, int mapping, int mode, const void* args,
                                int64_t nwaves, hipStream_t s) {
   DMT_DISPATCH(k, (launch_block_t<Mdl, T>(mapping, mode, args, nwaves, s)));
@@ -5993,10 +5472,10 @@ hipError_t DMT_ENTRY(launch_pathll_kernel)(const ModelKey& k, int mapping, const
   DMT_DISPATCH(k, (launch_pathll_t<Mdl, T>(mapping, args, nwaves, s)));
 }
 
-#endif  // !DMT_SPLIT || DMT_TU_GROUP >= 0
+#endif  // DMT_TU_GROUP >= 0
 
-#if DMT_SPLIT && DMT_TU_GROUP < 0
-// the split build's dispatchers: the (precision, model) group's translation unit
+#if DMT_TU_COMMON
+// the dispatchers: the (precision, model) group's translation unit
 #define DMT_DECL_GROUP(G)                                                                        \
   hipError_t launch_block_kernel_g##G(const ModelKey&, int, int, const void*, int64_t, hipStream_t); \
   hipError_t launch_mcmc_service_g##G(const ModelKey&, const void*, const AcceptArgs&, int64_t,    \
@@ -6055,9 +5534,7 @@ hipError_t launch_pathll_kernel(const ModelKey& k, int mapping, const void* args
                                 hipStream_t s) {
   DMT_FORWARD(hipErrorInvalidValue, launch_pathll_kernel, k, mapping, args, nwaves, s);
 }
-#endif  // DMT_SPLIT && DMT_TU_GROUP < 0
 
-#if DMT_TU_COMMON
 hipError_t launch_backward_filter(int precision, const FilterArgs& a, hipStream_t s) {
   const int64_t n = a.b1 - a.b0;
   if (n <= 0) return hipSuccess;
@@ -6325,7 +5802,7 @@ hipError_t launch_debug_philox(uint64_t seed, const uint32_t* ctr, int64_t n, ui
 #endif  // DMT_TU_COMMON
 }  // namespace dmt
 
-#if DMT_AUX_CHECK && !DMT_SPLIT
+#if DMT_AUX_CHECK && DMT_TU_GROUP == 0  // read from the fp64 OU unit (scripts/td_fault_probe.py)
 extern "C" int dmt_debug_aux_check(unsigned long long* out, int n) {
   // out[0] = count of out-of-table aux reads, then up to kAuxDbg records of 8 words
   // (block, segment, kind, row, step, chunk start, chunk count, table present); resets them

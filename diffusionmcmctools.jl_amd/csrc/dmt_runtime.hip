@@ -999,7 +999,8 @@ dmt_status dmt_create(dmt_ens** out, const dmt_model* model, const dmt_structure
   }
   h->tw = h->mapping == MAP_WAVE ? 1 : kLanes;
   // lane packets: the path planes of an fp32 lane-mapped ensemble (non-linear
-  // drift; OU ensembles are wave-mapped) in 16-point pieces per lane; DMT_PATH_PACKETS=0: rows
+  // drift; OU ensembles are wave-mapped) in packets of 32 points (128 B) per lane, staged by
+  // the kernels in 16-point pieces; with DMT_PATH_PACKETS=0 the planes are stored as rows
   h->pk = (h->mapping == MAP_LANE && model->precision == DMT_F32) ? kPathPacket : 0;
   if (const char* e = std::getenv("DMT_PATH_PACKETS")) h->pk = std::atoi(e) == 0 ? 0 : h->pk;
   h->ntiles = (h->R + h->tw - 1) / h->tw;

@@ -1,6 +1,7 @@
 #!/bin/bash
-# Copy a final session pair's evidence (gpurun_out/<A>, gpurun_out/<B>: scripts/sessions/
-# r05_finalA.sh, r05_finalC.sh with TAG=<A>, TAG=<B>) into profiles/<A>, profiles/<B> and write the kstats, traffic and
+# Copy a final session pair's evidence (the output directories <A>, <B> of the two final
+# sessions, whose scripts are in git history under scripts/sessions/) into profiles/<A>,
+# profiles/<B> and write the kstats, traffic and
 # issue summaries bench.py quotes (each stamped with the digest the session recorded).
 # usage: scripts/final_summaries.sh r05ia r05ib
 set -e

@@ -1,8 +1,10 @@
 #!/bin/bash
-# Register / scratch / LDS use of the kernels whose names match $1 (regex), gfx950 build.
-cd "$(dirname "$0")/../diffusionmcmctools.jl_amd/csrc"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result \
-  ${EXTRA_FLAGS} -c dmt_kernels.hip -o /tmp/dmt_kernels_ru.o -Rpass-analysis=kernel-resource-usage 2>&1 |
+# Register / scratch / LDS use of the built kernels whose names match $1 (regex): a filter over
+# the resource-usage remarks the build keeps beside each kernel object: build_obj/*.ru, or, for
+# a `make variants VARIANT_NAME=<name>` build, OBJDIR=build_variants/obj_<name> (both relative to
+# the repository root, where the Makefile's OBJDIR and VARIANTS_DIR point).
+cd "$(dirname "$0")/.."
+cat "${OBJDIR:-build_obj}"/dmt_kernels_*.o.ru |
   python3 -c '
 import re, sys
 pat = re.compile(sys.argv[1]); cur = None; out = {}

@@ -21,7 +21,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OBJ = os.path.join(ROOT, "build_obj")
-SRC = os.path.join(ROOT, "diffusionmcmctools.jl_amd", "csrc", "dmt_kernels.hip")
+CSRC = os.path.join(ROOT, "diffusionmcmctools.jl_amd", "csrc")
 
 FIELDS = ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize", "SGPRs Spill", "VGPRs Spill",
           "LDS Size", "Occupancy")
@@ -68,13 +68,25 @@ def _demangle(names):
     return dict(zip(names, out))
 
 
+def kernel_sources():
+    """The files a kernel object is built from: the Makefile's SRCS and HDRS, but for
+    dmt_runtime.hip (no prerequisite of a kernel object: make rewrites no .ru file for it)."""
+    text = open(os.path.join(CSRC, "Makefile")).read().replace("\\\n", " ")
+    names = []
+    for var in ("SRCS", "HDRS"):
+        names += re.search(r"^%s := (.*)$" % var, text, re.M).group(1).split()
+    assert "dmt_kernels.hip" in names and len(names) > 2, names
+    return [os.path.join(CSRC, n) for n in names if n != "dmt_runtime.hip"]
+
+
 def load_usage():
     files = sorted(glob.glob(os.path.join(OBJ, "dmt_kernels_*.o.ru")))
     if not files:
         pytest.skip("no resource-usage files: build the library first (make -C "
                     "diffusionmcmctools.jl_amd/csrc, or __graft_entry__.build())")
-    if any(os.path.getmtime(f) < os.path.getmtime(SRC) for f in files):
-        pytest.skip("resource-usage files older than dmt_kernels.hip: rebuild")
+    newest = max(os.path.getmtime(s) for s in kernel_sources())
+    if any(os.path.getmtime(f) < newest for f in files):
+        pytest.skip("resource-usage files older than the kernel sources: rebuild")
     usage, cur = {}, None
     for f in files:
         for line in open(f, errors="replace"):
