@@ -25,7 +25,7 @@ PATH_X, PATH_W, PATH_DW = 0, 1, 2  # dmt_download_paths `what`
 LAW_PP, LAW_PPB = 0, 1
 SWAP_XX, SWAP_WW, SWAP_PP, SWAP_LL = 1, 2, 4, 8
 BLK_LL, BLK_LLPROP, BLK_LL_HIST, BLK_LLPROP_HIST, BLK_ACC_HIST = 0, 1, 2, 3, 4
-K_DRAW, K_ACCEPT, K_PATHLL, K_RECOMPUTE, K_REDUCE = 0, 1, 2, 3, 4
+K_DRAW, K_ACCEPT, K_PATHLL, K_RECOMPUTE, K_REDUCE, K_MOMENTS = 0, 1, 2, 3, 4, 5
 # device random streams (include/dmt.h): salt = RNG_AUTO draws from the handle's counter
 RNG_AUTO = 0xFFFFFFFF
 SALT_LIMIT = 0x40000000
@@ -59,6 +59,8 @@ SYMBOLS = [
     "dmt_guiding_linear_tda",
     "dmt_get_rho", "dmt_set_rho", "dmt_accept_counts", "dmt_adapt_rho", "dmt_set_run_adaptation",
     "dmt_adapt_rule",
+    "dmt_moments_reserve", "dmt_moments_reset", "dmt_moments_accumulate", "dmt_set_run_moments",
+    "dmt_moments_state", "dmt_moments_download", "dmt_moments_upload", "dmt_moments_rule",
 ]
 
 
@@ -172,6 +174,14 @@ _SIGS = {
     "dmt_adapt_rho": [_P, _i32, _i64, _i64, _i64, C.POINTER(dmt_adapt_config), _pi64],
     "dmt_set_run_adaptation": [_P, _i32, C.POINTER(dmt_adapt_config)],
     "dmt_adapt_rule": [C.POINTER(dmt_adapt_config), _i64, _i64, _pd, _pi64, _pd, _pd],
+    "dmt_moments_reserve": [_P, _i32],
+    "dmt_moments_reset": [_P],
+    "dmt_moments_accumulate": [_P, _i64],
+    "dmt_set_run_moments": [_P, _i64, _i64],
+    "dmt_moments_state": [_P, _pi64, _pi64],
+    "dmt_moments_download": [_P, _pd, _pd, _pi64],
+    "dmt_moments_upload": [_P, _pd, _pd, _i64],
+    "dmt_moments_rule": [_i64, _i64, _pd, _pd, _pd, _pd, _pd],
 }
 for _name, _args in _SIGS.items():
     _f = getattr(lib, _name)

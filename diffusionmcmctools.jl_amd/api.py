@@ -27,7 +27,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib as L
-from .engine import Ensemble
+from .engine import Ensemble, moments_rule
 
 def _key(iter, salt):
     """(iter, salt) of a draw: no key given → the handle's stream counter (RNG_AUTO)."""
@@ -85,6 +85,37 @@ def _aux_callable(AuxLaw):
 
 
 # ============================================================================ sampling units
+class _HostMoments:
+    """Posterior path moments of an engine without ``moments_*`` methods (the oracle engine of
+    the test seam): ``download_paths(U, 0)`` folded on the host with ``engine.moments_rule``, the
+    rule the device kernel runs, so both backends serve the same calls with the same bits."""
+
+    def __init__(self, ens):
+        self.ens, self.every, self.from_ = ens, 0, 0
+        self.mean = self.m2 = None
+        self.n = self.last = 0
+
+    def accumulate(self, mcmciter):
+        x = np.ascontiguousarray(self.ens.download_paths(L.U, 0), dtype=np.float64)
+        if self.mean is None:
+            self.mean, self.m2 = np.zeros_like(x), np.zeros_like(x)
+        self.n += 1
+        moments_rule(x, self.mean, self.m2, self.n, out=(self.mean, self.m2))
+        self.last = int(mcmciter)
+
+    def run(self, ens_run, iter0, n_iter):
+        """``ens_run(iter0, n)`` cut after every due iteration, as dmt_mcmc_run cuts a run."""
+        out, it, end = [], int(iter0), int(iter0) + int(n_iter)
+        while it < end:
+            cut = -(-max(it, self.from_) // self.every) * self.every
+            n = min(end - it, cut - it + 1)
+            out.append(ens_run(it, n))
+            it += n
+            if it - 1 == cut:
+                self.accumulate(cut)
+        return np.concatenate(out) if out else np.empty((0, 3))
+
+
 class SamplingEnsemble:
     """``SamplingEnsemble(aux_laws, recordings, tts, …)`` (src/sampling_ensemble.jl:13-41):
     the u/u° containers of every recording, resident on one GPU.
@@ -356,6 +387,67 @@ class SamplingEnsemble:
 
     def ens_slots(self):
         return getattr(self.ens, "_snap_slots", 0)
+
+    # ---- posterior path moments: the smoothing estimate the tutorials form on the host from
+    # the kept copies of XX (docs/src/tutorials/biblock/smoothing.md:37-57), accumulated on the
+    # device (include/dmt.h, "posterior path moments")
+    def _host_moments(self):
+        hm = getattr(self.ens, "_host_moments", None)
+        if hm is None:
+            raise RuntimeError("no path moments: call reserve_path_moments() first")
+        return hm
+
+    def reserve_path_moments(self):
+        """Allocate (or zero again) the running mean and sum of squared deviations of every
+        recording's accepted path ``u.XX``."""
+        if hasattr(self.ens, "moments_reserve"):
+            self.ens.moments_reserve(True)
+        else:
+            self.ens._host_moments = _HostMoments(self.ens)
+
+    def accumulate_path_moments(self, mcmciter=0):
+        """Fold the current ``u.XX`` into the moments (Welford's update, fp64), on the device
+        without a host round trip."""
+        if hasattr(self.ens, "moments_accumulate"):
+            self.ens.moments_accumulate(mcmciter)
+        else:
+            self._host_moments().accumulate(mcmciter)
+
+    def path_moments_every(self, every, burn_in=0):
+        """Accumulate inside later ``mcmc_run`` calls after every iteration i with
+        i % every == 0 and i > burn_in; 0 turns it off.  An accumulation streams the whole
+        ensemble once, about the bytes of a draw, hence ``every``."""
+        if every < 0 or burn_in < 0:
+            raise ValueError("every and burn_in must be >= 0")
+        if hasattr(self.ens, "set_run_moments"):
+            self.ens.set_run_moments(every, burn_in + 1)
+        else:
+            hm = self._host_moments()
+            hm.every, hm.from_ = int(every), int(burn_in) + 1
+
+    def path_moments(self, var=True):
+        """``(mean, var, n)``: per recording the lists of per-segment (npts × d) arrays of the
+        posterior mean path and its pointwise variance ``m2 / (n − 1)``, and the number of
+        accumulated samples.  ``var=False`` returns ``None`` for the variance; otherwise n < 2
+        is refused."""
+        if hasattr(self.ens, "moments_download"):
+            mean, m2, n = self.ens.moments_download()
+        else:
+            hm = self._host_moments()
+            mean, m2, n = hm.mean, hm.m2, hm.n
+        if n < (2 if var else 1):
+            raise ValueError(f"path moments hold {n} samples: need {2 if var else 1}")
+
+        def split(A):
+            out, p = [], 0
+            for r in self.n_points:
+                segs = []
+                for k in r:
+                    segs.append(A[p:p + k])
+                    p += k
+                out.append(segs)
+            return out
+        return split(mean), (split(m2 / (n - 1)) if var else None), n
 
     def close(self):
         self.ens.close()
@@ -692,8 +784,12 @@ class _BlockRange:
         docs/src/tutorials/biblock/smoothing.md:40-44.  Without ``salt`` it draws exactly what
         the loop of counter-keyed :meth:`draw_proposal_path` / :meth:`accept_reject_proposal_path`
         calls would."""
-        return self._call("mcmc_run", iter0, n_iter,
-                          salt=L.RNG_AUTO if salt is None else int(salt), local=not self._global)
+        salt = L.RNG_AUTO if salt is None else int(salt)
+        hm = getattr(self._ens, "_host_moments", None)
+        if hm is not None and hm.every > 0:  # engines without device moments (_HostMoments)
+            return hm.run(lambda it, n: self._call("mcmc_run", it, n, salt=salt,
+                                                   local=not self._global), iter0, n_iter)
+        return self._call("mcmc_run", iter0, n_iter, salt=salt, local=not self._global)
 
 
 # recompute_guiding_term! flags (src/block_collection.jl:208-221) → units, in call order

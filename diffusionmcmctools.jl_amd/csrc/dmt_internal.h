@@ -211,6 +211,36 @@ struct AdaptArgs {
   uint32_t* n_changed;      // the blocks whose ρ changed are added here
 };
 
+// Posterior path moments (include/dmt.h, "posterior path moments"): Welford's update of one
+// element, the one definition the kernel (k_path_moments_*), the host entry point
+// (dmt_moments_rule) and the tests' NumPy restatement share.  n >= 1 is the new count.  Every −,
+// +, / and * is a separately rounded fp64 operation (the build has -ffp-contract=off; the division
+// is a true one), so host and device give the same bits.
+__host__ __device__ __forceinline__ void moments_rule(double x, double n, double* mean, double* m2) {
+  const double delta = x - *mean;
+  const double mn = *mean + delta / n;
+  *m2 = *m2 + delta * (x - mn);
+  *mean = mn;
+}
+
+// k_path_moments_*: fold u.XX (the buffer d_sel[0] names per segment) into the accumulators, which
+// are fp64 planes in the geometry of the X planes (plane_ix with the same tw, pk, tile_qoff, C = d)
+struct MomentArgs {
+  const void* X[3];          // path buffers (T); X[2] nullptr on two-buffer ensembles
+  const uint8_t* selX;       // [G] path selectors (sel_u)
+  double* mean;              // [plane elements]
+  double* m2;
+  const int64_t* tile_qoff;  // [ntiles + 1]
+  const int32_t* seg_q;      // [G]
+  const int32_t* seg_np;     // [G]
+  const int32_t* rec_g0;     // [R] first / last global segment of each recording (the internal
+  const int32_t* rec_g1;     //     layout 0: one block per recording)
+  int64_t R;
+  int C, tw, pk;
+  int64_t maxQ;              // most points of any recording
+  double n;                  // the new count, as the rule takes it
+};
+
 // The resident MCMC service (include/dmt.h "deferred draws"): a launch of the
 // register-resident producer/consumer kernel that runs the iterations the host posts one at a
 // time, keeping every block's state in registers between the caller's separate calls.
@@ -375,6 +405,8 @@ hipError_t launch_from_planes(int precision, int tw, double* dst, const void* sr
                               const int64_t* pt_off, int64_t G, const int32_t* seg_rec,
                               const int32_t* seg_q, const int64_t* tile_qoff, hipStream_t s,
                               const void* src2 = nullptr, int enc = 0, int pk = 0);
+// dmt_moments_accumulate: k_path_moments_{wave,rows,pk}<T> by (tw, pk)
+hipError_t launch_path_moments(int precision, const MomentArgs& a, hipStream_t s);
 hipError_t launch_cast(int precision, const double* src, void* dst, int64_t n, hipStream_t s);
 hipError_t launch_cast_back(int precision, const void* src, double* dst, int64_t n, hipStream_t s);
 hipError_t launch_block_sum(const double* ll, const double* llp, const uint8_t* acc, int64_t n,

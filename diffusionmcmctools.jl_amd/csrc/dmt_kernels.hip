@@ -4897,6 +4897,194 @@ __global__ void k_from_planes(const int tw, double* __restrict__ dst, const T* s
   dst[e] = (double)(slot == 0 ? src0 : slot == 1 ? src1 : src2)[o];
 }
 
+#if DMT_TU_COMMON
+// ---------------------------------------------------------------- posterior path moments
+// dmt_moments_accumulate (include/dmt.h): fold u.XX into the fp64 accumulators by moments_rule.
+// The accumulators are planes in the geometry of X (plane_ix, C = d), so the accumulator element
+// of a point has the point's own element index and every stream coalesces as the draw kernels' do.
+// A point's source buffer is the one its segment's selector names (sel_u); its segment comes from
+// a lookup (mom_find) or a walk within its own recording's segments [g0, g1], never from a search
+// over all G.  Only real points are touched: padding rows, tile tails and empty tile slots are
+// neither read nor written.  Three kernels, one per geometry (launch_path_moments).
+
+// largest g in [g0, g1] with seg_q[g] <= q (the segments of one recording)
+__device__ __forceinline__ int mom_find(const int32_t* __restrict__ seg_q, int g0, int g1, int q) {
+  int lo = g0, hi = g1 + 1;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (seg_q[mid] <= q) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+template <class T>
+__device__ __forceinline__ const T* mom_src(const MomentArgs& a, int g) {
+  return static_cast<const T*>(a.X[sel_u(a.selX[g])]);
+}
+
+// tw = 1 (wave mapping, every OU ensemble): a recording's points are one contiguous run of
+// Q·C elements; consecutive lanes take consecutive elements of one recording (blockIdx.x).
+template <class T>
+__global__ __launch_bounds__(256) void k_path_moments_wave(const MomentArgs a) {
+  const int64_t r = blockIdx.x;
+  const int g0 = a.rec_g0[r], g1 = a.rec_g1[r];
+  const int C = a.C;
+  const int64_t ne = (int64_t)(a.seg_q[g1] + a.seg_np[g1]) * C;
+  const int64_t base = a.tile_qoff[r] * C;
+  double* __restrict__ mean = a.mean + base;
+  double* __restrict__ m2 = a.m2 + base;
+  const T* __restrict__ X = mom_src<T>(a, g0) + base;
+  for (int64_t e = (int64_t)blockIdx.y * 256 + threadIdx.x; e < ne; e += (int64_t)gridDim.y * 256) {
+    if (g0 != g1) X = mom_src<T>(a, mom_find(a.seg_q, g0, g1, (int)(e / C))) + base;
+    double mu = mean[e], s = m2[e];
+    moments_rule((double)X[e], a.n, &mu, &s);
+    mean[e] = mu;
+    m2[e] = s;
+  }
+}
+
+// tw = 64, row layout (fp64 lane mapping): a lane per recording of a tile (blockIdx.x), each
+// wave marching over its own run of kMomRows rows; one wave access is 64 consecutive elements
+// per component (512 B of fp64), and each lane advances its own segment cursor.
+constexpr int kMomRows = 32;
+constexpr int kMomBatch = 4;  // rows a lane loads together while they stay in one segment
+template <class T, int C>
+__global__ __launch_bounds__(256) void k_path_moments_rows(const MomentArgs a) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t tile = blockIdx.x;
+  const int64_t r = tile * kLanes + lane;
+  if (r >= a.R) return;
+  const int g0 = a.rec_g0[r], g1 = a.rec_g1[r];
+  const int Q = a.seg_q[g1] + a.seg_np[g1];
+  const int64_t tq = a.tile_qoff[tile];
+  double* __restrict__ mean = a.mean;
+  double* __restrict__ m2 = a.m2;
+  for (int64_t qa = ((int64_t)blockIdx.y * 4 + wv) * kMomRows; qa < Q;
+       qa += (int64_t)gridDim.y * 4 * kMomRows) {
+    const int qb = (int)(qa + kMomRows < Q ? qa + kMomRows : Q);
+    int g = mom_find(a.seg_q, g0, g1, (int)qa);
+    int gend = a.seg_q[g] + a.seg_np[g];
+    const T* __restrict__ X = mom_src<T>(a, g);
+    for (int q = (int)qa; q < qb;) {
+      while (q >= gend && g < g1) {
+        ++g;
+        gend += a.seg_np[g];
+        X = mom_src<T>(a, g);
+      }
+      const int64_t ix0 = (tq + q) * C * kLanes + lane;
+      if (q + kMomBatch <= qb && q + kMomBatch <= gend) {
+        // kMomBatch rows of one segment: every load issued before the first use
+        double x[kMomBatch * C], mu[kMomBatch * C], s[kMomBatch * C];
+#pragma unroll
+        for (int k = 0; k < kMomBatch * C; ++k) {
+          x[k] = (double)X[ix0 + (int64_t)k * kLanes];
+          mu[k] = mean[ix0 + (int64_t)k * kLanes];
+          s[k] = m2[ix0 + (int64_t)k * kLanes];
+        }
+#pragma unroll
+        for (int k = 0; k < kMomBatch * C; ++k) {
+          moments_rule(x[k], a.n, &mu[k], &s[k]);
+          mean[ix0 + (int64_t)k * kLanes] = mu[k];
+          m2[ix0 + (int64_t)k * kLanes] = s[k];
+        }
+        q += kMomBatch;
+      } else {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          const int64_t ix = ix0 + (int64_t)c * kLanes;
+          double mu = mean[ix], s = m2[ix];
+          moments_rule((double)X[ix], a.n, &mu, &s);
+          mean[ix] = mu;
+          m2[ix] = s;
+        }
+        ++q;
+      }
+    }
+  }
+}
+
+// tw = 64, lane packets (fp32 lane mapping): kPathPacket consecutive rows of one component of
+// one tile slot are 128 contiguous bytes of X and 256 of each accumulator.  kMomLpp = 8 lanes
+// share a packet, each on a 4-point piece (one 16-byte load of X, two 16-byte loads and stores
+// per accumulator), and a wave covers 8 neighbouring slots: 1 KB of X and 2 KB of each
+// accumulator, contiguous, per wave access.  A lane keeps its slot and its piece of the packet
+// and marches over the packet rows with its own segment cursor; a piece that straddles a segment
+// end or the recording's first or last point goes element by element.
+constexpr int kMomLpp = kPathPacket / 4;     // lanes per packet
+constexpr int kMomSpw = kLanes / kMomLpp;    // slots per wave
+constexpr int kMomPackets = 4;               // packet rows per wave and pass
+static_assert(kPathPacket % 4 == 0 && kLanes % kMomLpp == 0, "4-point pieces tile a packet");
+template <int C>
+__global__ __launch_bounds__(256) void k_path_moments_pk(const MomentArgs a) {
+  constexpr int PK = kPathPacket;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t tile = blockIdx.x;
+  const int slot = (int)blockIdx.y * kMomSpw + lane / kMomLpp;
+  const int j0 = (lane % kMomLpp) * 4;
+  const int64_t r = tile * kLanes + slot;
+  if (r >= a.R) return;
+  const int g0 = a.rec_g0[r], g1 = a.rec_g1[r];
+  const int Q = a.seg_q[g1] + a.seg_np[g1];
+  const int64_t tq = a.tile_qoff[tile];
+  const int64_t p0 = tq / PK;                      // the recording's packet rows p0 .. p0 + np − 1
+  const int64_t np = (tq + Q - 1) / PK - p0 + 1;
+  double* __restrict__ mean = a.mean;
+  double* __restrict__ m2 = a.m2;
+  for (int64_t pa = ((int64_t)blockIdx.z * 4 + wv) * kMomPackets; pa < np;
+       pa += (int64_t)gridDim.z * 4 * kMomPackets) {
+    const int64_t pb = pa + kMomPackets < np ? pa + kMomPackets : np;
+    int g = g0, gbeg = 0, gend = a.seg_np[g0];
+    {
+      const int64_t q = (p0 + pa) * PK + j0 - tq;
+      if (q > 0) {
+        g = mom_find(a.seg_q, g0, g1, (int)(q < Q ? q : Q - 1));
+        gbeg = a.seg_q[g];
+        gend = gbeg + a.seg_np[g];
+      }
+    }
+    for (int64_t p = pa; p < pb; ++p) {
+      const int64_t q = (p0 + p) * PK + j0 - tq;  // the piece holds points q .. q + 3
+      if (q + 3 < 0 || q >= Q) continue;
+      while (q >= gend && g < g1) {
+        ++g;
+        gbeg = gend;
+        gend += a.seg_np[g];
+      }
+      const bool whole = q >= gbeg && q + 4 <= gend;
+      const float* __restrict__ X = mom_src<float>(a, g);
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const int64_t ix = (((p0 + p) * C + c) * kLanes + slot) * PK + j0;
+        if (whole) {
+          const float4 x = *reinterpret_cast<const float4*>(X + ix);
+          double2 mu0 = reinterpret_cast<const double2*>(mean + ix)[0];
+          double2 mu1 = reinterpret_cast<const double2*>(mean + ix)[1];
+          double2 s0 = reinterpret_cast<const double2*>(m2 + ix)[0];
+          double2 s1 = reinterpret_cast<const double2*>(m2 + ix)[1];
+          moments_rule((double)x.x, a.n, &mu0.x, &s0.x);
+          moments_rule((double)x.y, a.n, &mu0.y, &s0.y);
+          moments_rule((double)x.z, a.n, &mu1.x, &s1.x);
+          moments_rule((double)x.w, a.n, &mu1.y, &s1.y);
+          reinterpret_cast<double2*>(mean + ix)[0] = mu0;
+          reinterpret_cast<double2*>(mean + ix)[1] = mu1;
+          reinterpret_cast<double2*>(m2 + ix)[0] = s0;
+          reinterpret_cast<double2*>(m2 + ix)[1] = s1;
+        } else {
+          for (int j = 0; j < 4; ++j) {
+            const int64_t qq = q + j;
+            if (qq < 0 || qq >= Q) continue;
+            const float* Xj = mom_src<float>(a, mom_find(a.seg_q, g0, g1, (int)qq));
+            double mu = mean[ix + j], s = m2[ix + j];
+            moments_rule((double)Xj[ix + j], a.n, &mu, &s);
+            mean[ix + j] = mu;
+            m2[ix + j] = s;
+          }
+        }
+      }
+    }
+  }
+}
+#endif  // DMT_TU_COMMON
+
 template <class T>
 __global__ void k_cast(const double* __restrict__ src, T* __restrict__ dst, int64_t n) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -5683,6 +5871,51 @@ hipError_t launch_from_planes(int precision, int tw, double* dst, const void* sr
                                                        pt_off, G, seg_rec, seg_q,
                                                        tile_qoff, pk);
   return hipGetLastError();
+}
+
+// dmt_moments_accumulate: the kernel of the ensemble's geometry (wave mapping; lane mapping in
+// rows; lane mapping in packets, which only fp32 ensembles have)
+template <class T>
+static hipError_t launch_path_moments_t(const MomentArgs& a, hipStream_t s) {
+  constexpr unsigned kMaxGridYZ = 65535;
+  auto chunks = [](int64_t n, int64_t per) {
+    const int64_t c = (n + per - 1) / per;
+    return (unsigned)(c < 1 ? 1 : c > kMaxGridYZ ? kMaxGridYZ : c);
+  };
+  if (a.tw == 1) {
+    dlaunch(k_path_moments_wave<T>, dim3((unsigned)a.R, chunks(a.maxQ * a.C, 256)), dim3(256), s, a);
+    return hipGetLastError();
+  }
+  if (a.tw != kLanes || a.C < 1 || a.C > 3) return hipErrorInvalidValue;
+  const unsigned tiles = (unsigned)((a.R + kLanes - 1) / kLanes);
+  if (a.pk == 0) {
+    const dim3 grid(tiles, chunks(a.maxQ, 4 * kMomRows));
+    switch (a.C) {
+      case 1: dlaunch(k_path_moments_rows<T, 1>, grid, dim3(256), s, a); break;
+      case 2: dlaunch(k_path_moments_rows<T, 2>, grid, dim3(256), s, a); break;
+      default: dlaunch(k_path_moments_rows<T, 3>, grid, dim3(256), s, a); break;
+    }
+    return hipGetLastError();
+  }
+  if constexpr (std::is_same<T, float>::value) {
+    if (a.pk != kPathPacket) return hipErrorInvalidValue;
+    // a recording of Q points starting one point before a packet boundary spans at most
+    // 2 + (Q − 1) / pk packet rows
+    const dim3 grid(tiles, kLanes / kMomSpw, chunks(2 + (a.maxQ - 1) / kPathPacket, 4 * kMomPackets));
+    switch (a.C) {
+      case 1: dlaunch(k_path_moments_pk<1>, grid, dim3(256), s, a); break;
+      case 2: dlaunch(k_path_moments_pk<2>, grid, dim3(256), s, a); break;
+      default: dlaunch(k_path_moments_pk<3>, grid, dim3(256), s, a); break;
+    }
+    return hipGetLastError();
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_path_moments(int precision, const MomentArgs& a, hipStream_t s) {
+  if (a.R <= 0) return hipSuccess;
+  return precision == DMT_F64 ? launch_path_moments_t<double>(a, s)
+                              : launch_path_moments_t<float>(a, s);
 }
 
 hipError_t launch_cast(int precision, const double* src, void* dst, int64_t n, hipStream_t s) {

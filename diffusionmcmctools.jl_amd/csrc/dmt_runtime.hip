@@ -162,6 +162,12 @@ struct dmt_ens {
   int64_t run_snap_next = 0;   // ... into this slot next (ring over snap_slots)
   double* d_snap[2] = {nullptr, nullptr};
   std::vector<int64_t> snap_iter, snap_unit;
+  // posterior path moments (dmt_moments_*): running mean and sum of squared deviations of u.XX,
+  // fp64 planes in the geometry of the X planes; n samples, the last one of iteration mom_last
+  double* d_mom[2] = {nullptr, nullptr};
+  int64_t mom_n = 0, mom_last = 0;
+  int64_t run_mom_every = 0, run_mom_from = 0;  // dmt_set_run_moments (every = 0: off)
+  int64_t maxQ = 0;                             // most points of any recording
   int mapping = MAP_LANE;  // thread mapping of the recursion kernels
   int tw = kLanes;         // tile width of the device layout (64 lane-mapped, 1 wave-mapped)
   hipStream_t stream = nullptr;
@@ -261,8 +267,8 @@ struct dmt_ens {
     int64_t units;  // kernel invocations the interval stands for (k_mcmc_scan: iterations)
   };
   std::vector<PendingTime> pending[DMT_K_COUNT];
-  double t_ms[DMT_K_COUNT] = {0, 0, 0, 0, 0};
-  int64_t t_cnt[DMT_K_COUNT] = {0, 0, 0, 0, 0};
+  double t_ms[DMT_K_COUNT] = {};
+  int64_t t_cnt[DMT_K_COUNT] = {};
   std::vector<hipEvent_t> free_events;
   // comm
   ncclComm_t comm = nullptr;
@@ -946,6 +952,7 @@ dmt_status dmt_create(dmt_ens** out, const dmt_model* model, const dmt_structure
   h->P = P;
   h->S = S;
   h->Q0 = recQ[0];
+  h->maxQ = *std::max_element(recQ.begin(), recQ.end());
   if (h->grid_shared) {
     for (int64_t r = 1; r < h->R; ++r) {
       if (h->rec_seg0[r + 1] - h->rec_seg0[r] != h->rec_seg0[1] - h->rec_seg0[0])
@@ -1131,6 +1138,8 @@ dmt_status dmt_destroy(dmt_ens* h) {
     }
   for (int k = 0; k < 2; ++k)
     if (h->d_snap[k]) (void)hipFree(h->d_snap[k]);
+  for (int k = 0; k < 2; ++k)
+    if (h->d_mom[k]) (void)hipFree(h->d_mom[k]);
   if (h->comm) (void)ncclCommDestroy(h->comm);
   if (h->h_red) (void)hipHostFree(h->h_red);
   if (h->h_run) (void)hipHostFree(h->h_run);
@@ -1833,16 +1842,19 @@ static dmt_status mcmc_run_impl(dmt_ens* h, int32_t layout, int64_t b0, int64_t 
   if (n_iter == 0) return DMT_OK;
   if (L->hist_len > 0 && iter0 + n_iter - 1 > L->hist_len)
     return fail(DMT_ERR_INVALID, "iterations outside 1:ll_hist_len");
-  if (h->run_snap_every > 0 || L->adapt.every > 0) {
+  if (h->run_snap_every > 0 || h->run_mom_every > 0 || L->adapt.every > 0) {
     // snapshots inside the run (the smoothing loop's `deepcopy(sp.u.XX)` every k iterations,
     // docs/src/tutorials/biblock/smoothing.md:40-44) and adaptation of ρ (dmt_set_run_adaptation):
-    // one cut loop serves both.  The run is cut after every iteration that is a multiple of
-    // either `every` (adaptation: up to its `until`); there u is snapshotted if due, then ρ of
-    // the run's range adapted if due, stream-ordered; the pieces take the same stream keys as
-    // one run (auto keys: consecutive counter values)
+    // and the path moments (dmt_set_run_moments): one cut loop serves all three.  The run is cut
+    // after every iteration that is a multiple of one of the `every` (moments: from their `from`;
+    // adaptation: up to its `until`); there u is snapshotted if due, then folded into the moments
+    // if due, then ρ of the run's range adapted if due, stream-ordered; the pieces take the same
+    // stream keys as one run (auto keys: consecutive counter values)
     const int64_t snap_every = h->run_snap_every;
+    const int64_t mom_every = h->run_mom_every, mom_from = h->run_mom_from;
     const dmt_adapt_config ad = L->adapt;
     h->run_snap_every = 0;
+    h->run_mom_every = 0;
     L->adapt.every = 0;
     // next multiple of `every` that is >= it
     auto next_cut = [](int64_t it, int64_t every) { return ((it + every - 1) / every) * every; };
@@ -1854,6 +1866,7 @@ static dmt_status mcmc_run_impl(dmt_ens* h, int32_t layout, int64_t b0, int64_t 
       const int64_t it = iter0 + done;
       int64_t n = n_iter - done;
       if (snap_every > 0) n = std::min(n, next_cut(it, snap_every) - it + 1);
+      if (mom_every > 0) n = std::min(n, next_cut(std::max(it, mom_from), mom_every) - it + 1);
       if (ad.every > 0 && adapts_at(next_cut(it, ad.every)))
         n = std::min(n, next_cut(it, ad.every) - it + 1);
       st = mcmc_run_impl(h, layout, b0, b1, it, n, salt, out ? out + 3 * done : nullptr, global);
@@ -1863,10 +1876,13 @@ static dmt_status mcmc_run_impl(dmt_ens* h, int32_t layout, int64_t b0, int64_t 
         st = dmt_snapshot_take(h, DMT_U, h->run_snap_next, last);
         h->run_snap_next = (h->run_snap_next + 1) % h->snap_slots;
       }
+      if (st == DMT_OK && mom_every > 0 && last % mom_every == 0 && last >= mom_from)
+        st = dmt_moments_accumulate(h, last);
       if (st == DMT_OK && adapts_at(last)) st = enter(h);
       if (st == DMT_OK && adapts_at(last)) st = adapt_rho_impl(h, L, b0, b1, last, &ad, nullptr);
     }
     h->run_snap_every = snap_every;
+    h->run_mom_every = mom_every;
     L->adapt = ad;
     return st;
   }
@@ -3176,6 +3192,158 @@ dmt_status dmt_snapshot_write(dmt_ens* h, const char* path, int64_t s0, int64_t 
   }
   if (std::fclose(f) != 0) ok = false;
   if (!ok) return fail(DMT_ERR_HIP, std::string("writing ") + path + " failed");
+  return DMT_OK;
+}
+
+// ---------------------------------------------------------------- posterior path moments
+// The smoothing tutorials form the posterior mean path and its spread on the host from the kept
+// copies of bb.b.XX (docs/src/tutorials/biblock/smoothing.md:37-57).  Here the running mean and
+// the running sum of squared deviations of u.XX live in HBM as two fp64 arrays in the geometry of
+// the X planes and take one streaming kernel per recorded iteration (include/dmt.h).
+
+static dmt_status moments_ready(dmt_ens* h) {
+  if (!h->d_mom[0]) return fail(DMT_ERR_STATE, "no path moments (dmt_moments_reserve)");
+  return DMT_OK;
+}
+
+static dmt_status moments_zero(dmt_ens* h) {
+  for (int k = 0; k < 2; ++k)
+    HIP_OK(hipMemsetAsync(h->d_mom[k], 0, plane_elems(h, h->d) * 8, h->stream));
+  h->mom_n = 0;
+  h->mom_last = 0;
+  return DMT_OK;
+}
+
+dmt_status dmt_moments_reserve(dmt_ens* h, int32_t enable) {
+  DMT_TRY(enter(h));
+  if (!enable) {
+    HIP_OK(stream_wait(h));
+    for (int k = 0; k < 2; ++k) {
+      if (!h->d_mom[k]) continue;
+      (void)hipFree(h->d_mom[k]);
+      h->bytes -= plane_elems(h, h->d) * 8;
+      h->d_mom[k] = nullptr;
+    }
+    h->mom_n = h->mom_last = 0;
+    h->run_mom_every = h->run_mom_from = 0;
+    return DMT_OK;
+  }
+  if (!h->d_mom[0]) {
+    double* p[2] = {nullptr, nullptr};
+    DMT_TRY(ens_alloc(h, &p[0], plane_elems(h, h->d)));
+    const dmt_status st = ens_alloc(h, &p[1], plane_elems(h, h->d));
+    if (st != DMT_OK) {
+      (void)hipFree(p[0]);
+      h->bytes -= plane_elems(h, h->d) * 8;
+      return st;
+    }
+    h->d_mom[0] = p[0];
+    h->d_mom[1] = p[1];
+  }
+  return moments_zero(h);
+}
+
+dmt_status dmt_moments_reset(dmt_ens* h) {
+  DMT_TRY(enter(h));
+  DMT_TRY(moments_ready(h));
+  return moments_zero(h);
+}
+
+dmt_status dmt_moments_accumulate(dmt_ens* h, int64_t mcmciter) {
+  DMT_TRY(enter(h));
+  DMT_TRY(moments_ready(h));
+  const Layout* L0 = h->layouts[0].get();  // one block per recording: its first / last segment
+  MomentArgs a{};
+  for (int s = 0; s < 3; ++s) a.X[s] = h->d_X[s];
+  a.selX = h->d_sel[0];
+  a.mean = h->d_mom[0];
+  a.m2 = h->d_mom[1];
+  a.tile_qoff = h->d_tile_qoff;
+  a.seg_q = h->d_seg_q;
+  a.seg_np = h->d_seg_np;
+  a.rec_g0 = L0->d_gfirst;
+  a.rec_g1 = L0->d_glast;
+  a.R = h->R;
+  a.C = h->d;
+  a.tw = h->tw;
+  a.pk = h->pk;
+  a.maxQ = h->maxQ;
+  a.n = (double)(h->mom_n + 1);
+  {
+    TimedScope ts(h, DMT_K_MOMENTS);
+    HIP_OK(launch_path_moments(h->key.precision, a, h->stream));
+  }
+  ++h->mom_n;
+  h->mom_last = mcmciter;
+  return DMT_OK;
+}
+
+dmt_status dmt_set_run_moments(dmt_ens* h, int64_t every, int64_t from) {
+  DMT_TRY(enter(h));
+  if (every < 0 || from < 0) return fail(DMT_ERR_INVALID, "every and from must be >= 0");
+  if (every > 0) DMT_TRY(moments_ready(h));
+  h->run_mom_every = every;
+  h->run_mom_from = every > 0 ? from : 0;
+  return DMT_OK;
+}
+
+dmt_status dmt_moments_state(dmt_ens* h, int64_t* n, int64_t* last_iter) {
+  DMT_TRY(check_h(h));
+  DMT_TRY(moments_ready(h));
+  if (n) *n = h->mom_n;
+  if (last_iter) *last_iter = h->mom_last;
+  return DMT_OK;
+}
+
+dmt_status dmt_moments_download(dmt_ens* h, double* mean, double* m2, int64_t* n) {
+  DMT_TRY(enter(h));
+  DMT_TRY(moments_ready(h));
+  double* out[2] = {mean, m2};
+  const int64_t ne = h->P * h->d;
+  for (int k = 0; k < 2; ++k) {
+    if (!out[k]) continue;
+    DMT_TRY(ensure_stage(h, ne));
+    HIP_OK(launch_from_planes(DMT_F64, h->tw, h->d_stage, h->d_mom[k], h->d_mom[k], nullptr, 0, h->d,
+                              h->P, h->d_pt_off, h->G, h->d_seg_rec, h->d_seg_q, h->d_tile_qoff,
+                              h->stream, nullptr, 0, h->pk));
+    HIP_OK(hipMemcpyAsync(out[k], h->d_stage, ne * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIP_OK(stream_wait(h));
+  if (n) *n = h->mom_n;
+  return DMT_OK;
+}
+
+dmt_status dmt_moments_upload(dmt_ens* h, const double* mean, const double* m2, int64_t n) {
+  DMT_TRY(enter(h));
+  DMT_TRY(moments_ready(h));
+  if (!mean || !m2) return fail(DMT_ERR_INVALID, "dmt_moments_upload: null array");
+  if (n < 0) return fail(DMT_ERR_INVALID, "dmt_moments_upload: n must be >= 0");
+  const double* in[2] = {mean, m2};
+  const int64_t ne = h->P * h->d;
+  DMT_TRY(ensure_stage(h, ne));
+  for (int k = 0; k < 2; ++k) {
+    HIP_OK(hipMemcpyAsync(h->d_stage, in[k], ne * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_OK(launch_to_planes(DMT_F64, h->tw, h->d_stage, h->d_mom[k], h->d_mom[k], nullptr, 0, h->d,
+                            h->P, h->d_pt_off, h->G, h->d_seg_rec, h->d_seg_q, h->d_tile_qoff,
+                            h->stream, 0, nullptr, 0, h->pk));
+  }
+  HIP_OK(stream_wait(h));  // the host buffers are the caller's
+  h->mom_n = n;
+  return DMT_OK;
+}
+
+dmt_status dmt_moments_rule(int64_t n, int64_t count, const double* x, const double* mean_in,
+                            const double* m2_in, double* mean_out, double* m2_out) {
+  if (n < 0 || count < 1) return fail(DMT_ERR_INVALID, "dmt_moments_rule: need n >= 0, count >= 1");
+  if (n > 0 && (!x || !mean_in || !m2_in || !mean_out || !m2_out))
+    return fail(DMT_ERR_INVALID, "dmt_moments_rule: null array");
+  const double cnt = (double)count;
+  for (int64_t j = 0; j < n; ++j) {
+    double mu = mean_in[j], s = m2_in[j];
+    moments_rule(x[j], cnt, &mu, &s);
+    mean_out[j] = mu;
+    m2_out[j] = s;
+  }
   return DMT_OK;
 }
 

@@ -372,6 +372,49 @@ class Ensemble:
         c = None if cfg is None else _adapt_struct(cfg)
         L.call("dmt_set_run_adaptation", self._h, layout, None if c is None else C.byref(c))
 
+    # ---------------------------------------------------------------- posterior path moments
+    def moments_reserve(self, enable=True):
+        """Allocate and zero (enable) or free the running mean / sum of squared deviations of
+        u.XX (include/dmt.h, "posterior path moments"); a second call zeroes them again."""
+        L.call("dmt_moments_reserve", self._h, 1 if enable else 0)
+
+    def moments_reset(self):
+        L.call("dmt_moments_reset", self._h)
+
+    def moments_accumulate(self, mcmciter=0):
+        """Fold the current u.XX into the accumulators on the device (no host wait)."""
+        L.call("dmt_moments_accumulate", self._h, int(mcmciter))
+
+    def set_run_moments(self, every, from_=0, **kw):
+        """Accumulate inside every later mcmc_run after each iteration i with i % every == 0
+        and i >= from (keyword ``from`` accepted too); every = 0: off."""
+        from_ = kw.pop("from", from_)
+        if kw:
+            raise TypeError(f"unexpected arguments {sorted(kw)}")
+        L.call("dmt_set_run_moments", self._h, int(every), int(from_))
+
+    def moments_state(self):
+        """(n, last_iter): accumulated samples and the mcmciter of the last one."""
+        n, last = C.c_int64(), C.c_int64()
+        L.call("dmt_moments_state", self._h, C.byref(n), C.byref(last))
+        return n.value, last.value
+
+    def moments_download(self):
+        """(mean, m2, n): [P][d] arrays in the layout of download_paths(U, 0)."""
+        mean = np.empty((self.P, self.d), dtype=np.float64)
+        m2 = np.empty((self.P, self.d), dtype=np.float64)
+        n = C.c_int64()
+        L.call("dmt_moments_download", self._h, L.f64p(mean), L.f64p(m2), C.byref(n))
+        return mean, m2, n.value
+
+    def moments_upload(self, mean, m2, n):
+        """Restore a checkpoint of moments_download."""
+        mean = np.ascontiguousarray(mean, dtype=np.float64)
+        m2 = np.ascontiguousarray(m2, dtype=np.float64)
+        if mean.size != self.P * self.d or m2.size != self.P * self.d:
+            raise ValueError("mean and m2 need P·d values each")
+        L.call("dmt_moments_upload", self._h, L.f64p(mean), L.f64p(m2), int(n))
+
     # ---------------------------------------------------------------- misc
     def sync(self):
         st = L.fast["dmt_sync"](self._h)
@@ -508,6 +551,23 @@ def adapt_rule(cfg, mcmciter, rho, counts):
     L.call("dmt_adapt_rule", C.byref(s), int(mcmciter), r.size, L.f64p(r),
            c.ctypes.data_as(C.POINTER(C.c_int64)), L.f64p(out), L.f64p(sout))
     return out, sout
+
+
+def moments_rule(x, mean, m2, count, out=None):
+    """Welford's update on host arrays (dmt_moments_rule; no device): returns (mean', m2') after
+    folding sample ``x`` as the ``count``-th one.  ``out=(mean_out, m2_out)`` writes into the
+    given float64 arrays, which may be ``mean`` and ``m2`` themselves."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    mean = np.ascontiguousarray(mean, dtype=np.float64)
+    m2 = np.ascontiguousarray(m2, dtype=np.float64)
+    if not (x.size == mean.size == m2.size):
+        raise ValueError("x, mean and m2 need the same size")
+    mo, so = (np.empty_like(mean), np.empty_like(m2)) if out is None else out
+    if mo.size != x.size or so.size != x.size:
+        raise ValueError("outputs need the inputs' size")
+    L.call("dmt_moments_rule", x.size, int(count), L.f64p(x), L.f64p(mean), L.f64p(m2),
+           L.f64p(mo), L.f64p(so))
+    return mo, so
 
 
 def comm_unique_id() -> bytes:

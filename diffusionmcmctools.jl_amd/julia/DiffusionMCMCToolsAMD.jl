@@ -38,7 +38,9 @@ import DiffusionMCMCTools: draw_proposal_path!, accept_reject_proposal_path!, lo
 export DeviceSamplingEnsemble, DeviceSamplingPair, DeviceSamplingUnit, DeviceBlockEnsemble,
     DeviceBlockCollection, DeviceBiBlock, DeviceBlock, use_device!, mcmc_step!, mcmc_run!,
     download_XX, download_WW, upload_obs!, snapshot_every!, law_record, guiding_linear, sync,
-    upload_aux!, upload_aux_a!, device_model, device_aux, adapt_ρ!, set_run_adaptation!
+    upload_aux!, upload_aux_a!, device_model, device_aux, adapt_ρ!, set_run_adaptation!,
+    reserve_path_moments!, reset_path_moments!, accumulate_path_moments!, path_moments_every!,
+    path_moments_state, path_moments, upload_path_moments!, moments_rule
 
 const libdmt = get(ENV, "DMT_LIB", joinpath(@__DIR__, "..", "libdmt.so"))
 
@@ -228,6 +230,51 @@ snapshot_every!(se::DeviceSamplingEnsemble, every; slot0=0) =
 write_snapshots(se::DeviceSamplingEnsemble, path::AbstractString, s0, s1) =
     check(ccall((:dmt_snapshot_write, libdmt), Int32, (Ptr{Cvoid}, Cstring, Int64, Int64),
                 se.h, path, s0, s1))
+
+# ---- posterior path moments: the running mean and sum of squared deviations of u.XX on the GPU
+# (include/dmt.h "posterior path moments") — the smoothing estimate the tutorials form on the host
+# from the kept copies of XX (docs/src/tutorials/biblock/smoothing.md:37-57)
+reserve_path_moments!(se::DeviceSamplingEnsemble; enable=true) =
+    check(ccall((:dmt_moments_reserve, libdmt), Int32, (Ptr{Cvoid}, Int32), se.h, enable ? 1 : 0))
+reset_path_moments!(se::DeviceSamplingEnsemble) =
+    check(ccall((:dmt_moments_reset, libdmt), Int32, (Ptr{Cvoid},), se.h))
+accumulate_path_moments!(se::DeviceSamplingEnsemble, mcmciter=0) =
+    check(ccall((:dmt_moments_accumulate, libdmt), Int32, (Ptr{Cvoid}, Int64), se.h, mcmciter))
+# inside mcmc_run!: after every iteration i with i % every == 0 and i > burn_in; every = 0: off
+path_moments_every!(se::DeviceSamplingEnsemble, every; burn_in=0) =
+    check(ccall((:dmt_set_run_moments, libdmt), Int32, (Ptr{Cvoid}, Int64, Int64),
+                se.h, every, burn_in + 1))
+function path_moments_state(se::DeviceSamplingEnsemble)
+    n = Ref{Int64}(0)
+    last = Ref{Int64}(0)
+    check(ccall((:dmt_moments_state, libdmt), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}),
+                se.h, n, last))
+    n[], last[]
+end
+"(mean, m2, n): Vector{SVector{d,Float64}} of all points, segments recording-major; var = m2 / (n − 1)"
+function path_moments(se::DeviceSamplingEnsemble)
+    mean = Vector{Float64}(undef, se.P * se.d)
+    m2 = Vector{Float64}(undef, se.P * se.d)
+    n = Ref{Int64}(0)
+    check(ccall((:dmt_moments_download, libdmt), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}), se.h, mean, m2, n))
+    collect(reinterpret(SVector{se.d,Float64}, mean)), collect(reinterpret(SVector{se.d,Float64}, m2)), n[]
+end
+function upload_path_moments!(se::DeviceSamplingEnsemble, mean, m2, n)
+    a = collect(reinterpret(Float64, mean))
+    b = collect(reinterpret(Float64, m2))
+    check(ccall((:dmt_moments_upload, libdmt), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64), se.h, a, b, n))
+end
+# the rule on host arrays (no device): x folded as the count-th sample
+function moments_rule(x::Vector{Float64}, mean::Vector{Float64}, m2::Vector{Float64}, count)
+    mo = similar(mean)
+    so = similar(m2)
+    check(ccall((:dmt_moments_rule, libdmt), Int32,
+                (Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                length(x), count, x, mean, m2, mo, so))
+    mo, so
+end
 
 "draw_proposal_path!(u::SamplingUnit) for recordings r0+1:r1 (src/sampling_unit.jl:118)."
 function draw_unit!(se::DeviceSamplingEnsemble, unit, r0, r1; Z=nothing, iter=nothing,

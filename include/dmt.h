@@ -74,7 +74,7 @@ enum {
 };
 /* kernels whose device time can be queried (dmt_get_timing) */
 enum { DMT_K_DRAW = 0, DMT_K_ACCEPT = 1, DMT_K_PATHLL = 2, DMT_K_RECOMPUTE = 3,
-       DMT_K_REDUCE = 4, DMT_K_COUNT = 5 };
+       DMT_K_REDUCE = 4, DMT_K_MOMENTS = 5 /* dmt_moments_accumulate */, DMT_K_COUNT = 6 };
 
 /*
  * Law record: one per segment per (unit, kind), DMT_LAW_STRIDE doubles.
@@ -582,6 +582,66 @@ dmt_status dmt_set_run_adaptation(dmt_ens* h, int32_t layout, const dmt_adapt_co
 dmt_status dmt_adapt_rule(const dmt_adapt_config* cfg, int64_t mcmciter, int64_t n,
                           const double* rho_in, const int64_t* counts, double* rho_out,
                           double* srho_out);
+
+/* ---------------- posterior path moments ----------------
+ * The reference has no counterpart: its smoothing tutorials keep `deepcopy(bb.b.XX)` every few
+ * hundred iterations and form every statistic of the cloud on the host
+ * (docs/src/tutorials/biblock/smoothing.md:37-57, smoothing_with_blocking.md).  These calls serve
+ * that caller code at sizes where a copy of XX is gigabytes: the running mean and the running sum
+ * of squared deviations of the accepted paths u.XX, one pair of fp64 values per path element,
+ * kept and updated on the device (snapshots, above, stay for plots of individual draws).
+ *
+ * The rule (Welford's update).  For a sample x (a double; an fp32 ensemble's value is cast to
+ * double first), the accumulators (mean, m2) of that element and the new count n >= 1:
+ *   delta = x − mean,   mean' = mean + delta / (double)n,   m2' = m2 + delta · (x − mean'),
+ * every −, +, /, · a separately rounded fp64 operation (a true division, no fused multiply-add), so
+ * the device, the host function dmt_moments_rule and a NumPy restatement give the same bits.  n is
+ * one number for the whole ensemble and lives in the handle.  The posterior mean path is `mean`,
+ * its pointwise variance m2 / (n − 1). */
+
+/* No reference counterpart (smoothing.md:37-57 as above).  enable != 0: allocates and zeroes the
+ * two accumulators for XX of unit u and sets n = 0 (a second call zeroes them again); enable = 0
+ * frees them (and turns dmt_set_run_moments off).  dmt_memory_bytes counts both; dmt_destroy
+ * frees them. */
+dmt_status dmt_moments_reserve(dmt_ens* h, int32_t enable);
+/* No reference counterpart (the caller's `paths = []`, smoothing.md:37): zeroes the accumulators
+ * and sets n = 0 without reallocating. */
+dmt_status dmt_moments_reset(dmt_ens* h);
+/* No reference counterpart; stands where the caller's loop has `append!(paths,
+ * [deepcopy(bb.b.XX)])` (smoothing.md:55).  Folds the current u.XX of the whole ensemble into the
+ * accumulators with n <- n + 1 and records mcmciter as last_iter, ordered on the handle's stream
+ * after every queued kernel (like any other call it first launches a deferred draw and stops the
+ * resident service); it does not block the host and touches neither paths, ll, histories,
+ * selectors nor the RNG state. */
+dmt_status dmt_moments_accumulate(dmt_ens* h, int64_t mcmciter);
+/* No reference counterpart; the `if i % save_every == 0` of the caller's loop (smoothing.md:40-57)
+ * inside dmt_mcmc_run / dmt_mcmc_run_local: from now on every run on this handle is cut after each
+ * iteration i with i % every == 0 and i >= from, and dmt_moments_accumulate(h, i) is queued there.
+ * At a cut the order is: run snapshot if due (dmt_set_run_snapshots), then the moments if due,
+ * then the adaptation of ρ if due (dmt_set_run_adaptation).  The pieces take the same stream keys
+ * as an unsplit run, so a run with moments on equals the loop of shorter runs and
+ * dmt_moments_accumulate calls, and its out, paths and histories equal those of the same run with
+ * moments off.  every = 0 turns it off.  Handle-level, like dmt_set_run_snapshots: u is shared by
+ * all layouts.
+ * Under a communicator (dmt_comm_init) a shard holds the moments of its own recordings and there
+ * is no collective, but every rank must install the same every / from: the cuts decide the
+ * sequence of all-gathers the ranks issue (as for dmt_set_run_adaptation). */
+dmt_status dmt_set_run_moments(dmt_ens* h, int64_t every, int64_t from);
+/* No reference counterpart (length(paths) of smoothing.md:55): the number of accumulated samples
+ * n and the mcmciter of the last one (0 before the first); either pointer may be NULL. */
+dmt_status dmt_moments_state(dmt_ens* h, int64_t* n, int64_t* last_iter);
+/* No reference counterpart (the statistics the caller forms from `paths`, smoothing.md:37-57):
+ * mean, m2: double[P][d] in the reference layout of dmt_download_paths(what = 0); either may be
+ * NULL, n is nullable.  Blocks the host. */
+dmt_status dmt_moments_download(dmt_ens* h, double* mean, double* m2, int64_t* n);
+/* No reference counterpart: restores a checkpoint (dmt_moments_download's arrays and n >= 0);
+ * accumulation then continues bit for bit as if never interrupted. */
+dmt_status dmt_moments_upload(dmt_ens* h, const double* mean, const double* m2, int64_t n);
+/* No reference counterpart: the rule above on host arrays of n elements with the new count
+ * count >= 1 (no device needed): (mean_out, m2_out)[j] from x[j], (mean_in, m2_in)[j].  The
+ * outputs may alias the inputs. */
+dmt_status dmt_moments_rule(int64_t n, int64_t count, const double* x, const double* mean_in,
+                            const double* m2_in, double* mean_out, double* m2_out);
 
 /* ---------------- random stream counter (DMT_RNG_AUTO) ---------------- */
 dmt_status dmt_rng_counter(dmt_ens* h, uint64_t* next);
